@@ -1,8 +1,11 @@
 """Benchmark: PageRank GTEPS per iteration + % of HBM roofline on R-MAT scale-26 (BASELINE.json).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--scale 26] [--graph rmat|er|lj|twitter]
+                    [--dump-outputs DIR] [--full]
 
-A step is one PageRank iteration (Sparky.java:189-235) over the whole graph, inputs resident
+A plain run generates and builds the graph, warms up, times the K steps, writes its outputs when
+--dump-outputs is given and prints the result line; --full adds the validation leg after the timed
+steps (cpu_baseline and parity below, null in a plain run's line).  A step is one PageRank iteration (Sparky.java:189-235) over the whole graph, inputs resident
 in HBM.  The graph is generated on the GPU (sparky_hip.workloads: seeded R-MAT, Graph500
 a/b/c = .57/.19/.19, edge factor 16), interned in first-appearance order (pr_intern_device) and
 built by libpagerank_hip; none of that is timed.  N > 1: one process per GPU under
@@ -17,15 +20,19 @@ value = E' (distinct edges of the whole graph) / (max-over-ranks time per step) 
 Rank 0 prints ONE JSON line (the driver's contract), including
   roofline:       algorithmic bytes per SpMV pass (12 E'_part + 36 V_part) divided
                   by the pass's mean HIP-event time on the library's stream, vs 8 TB/s;
-  cpu_baseline:   oracle/pagerank_oracle.c (OpenMP restatement of the same semantics) on this
+  outputs:        --dump-outputs DIR: after the timed steps rank 0 writes what the last step computed
+                  as float64 DIR/<name>.npy -- ranks (above 2^21 vertices a fixed seeded sample of
+                  them, ranks_index naming the vertices) and stats (dangling sum, L1 delta); the
+                  graph is seeded, so the same arguments give the same inputs on every run;
+  cpu_baseline:   (--full) oracle/pagerank_oracle.c (OpenMP restatement of the same semantics) on this
                   host's cores (N = 1 only): the median of iterations 2..K of the same graph;
-  parity_max_rel: after the timed region, K iterations from a fresh reset on the GPU (every
+  parity_max_rel: (--full) after the timed region, K iterations from a fresh reset on the GPU (every
                   rank's rows summed into one vector on rank 0 when N > 1) against K iterations
                   of the oracle on a CSR it builds itself from the raw interned edges, which the
                   exported canonical CSR must equal bit for bit (parity.csr_bit_exact) -- the
                   north-star 1e-9 bar;
   error (only on failure): a watchdog thread gives every stage (init, generate, build, attach,
-                  calibration, timed, parity) a deadline; a stage that overruns -- e.g. a hang
+                  calibration, timed, dump, parity) a deadline; a stage that overruns -- e.g. a hang
                   inside ncclCommInitRank or a collective on a first multi-GPU run -- makes rank 0
                   print the JSON line with "value": null and "error" naming the stage, and every
                   rank exit with status 3 (no re-exec; the process ends itself)
@@ -64,7 +71,7 @@ def log(msg: str) -> None:
     print(f"[bench] {msg}", file=sys.stderr, flush=True)
 
 
-STAGES = ("init", "generate", "build", "attach", "calibration", "timed", "parity")
+STAGES = ("init", "generate", "build", "attach", "calibration", "timed", "dump", "parity")
 
 
 class Watchdog:
@@ -504,6 +511,45 @@ def parity_runs(g, dist, rank: int, V: int, K: int, mode, ipc_ok: bool, all_mode
     return ref_merged, owned_once, checked, failed
 
 
+DUMP_MAX_RANKS = 1 << 21  # ranks + their indices as float64: at most 32 MiB, under the 64 MB a dump may take
+DUMP_SEED = 20261
+
+
+def dump_outputs(out_dir: str, g, dist, rank: int, V: int, st: dict, device: str = "cuda"):
+    """--dump-outputs: what the timed path computed in its last step, as float64 .npy files written
+    by rank 0 -- the ranks a caller reads with pr_get_ranks (every rank's rows summed on rank 0 when
+    N > 1: each vertex is owned by exactly one rank) and the last iteration's dangling sum and L1
+    delta (pr_get_stats).  Above DUMP_MAX_RANKS vertices the ranks are a fixed sample: the sorted
+    indices drawn without replacement by a generator seeded with DUMP_SEED, so two builds run with
+    the same arguments dump the same vertices.  Returns {name: shape} on rank 0."""
+    import numpy as np
+
+    mine = np.zeros(max(V, 1), np.float64)
+    g.ranks(mine)
+    mine = mine[:V]
+    if dist is not None:
+        import torch
+
+        rt = torch.from_numpy(mine).to(device)
+        dist.reduce(rt, dst=0, op=dist.ReduceOp.SUM)
+        if rank == 0:
+            mine = rt.cpu().numpy()
+        del rt
+    if rank != 0:
+        return None
+    if V > DUMP_MAX_RANKS:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(V, size=DUMP_MAX_RANKS, replace=False))
+    else:
+        idx = np.arange(V)
+    arrays = {"ranks": mine[idx], "ranks_index": idx.astype(np.float64),
+              "stats": np.array([st["last_dc"], st["last_l1"]], np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(arr, dtype=np.float64))
+    log(f"dumped {', '.join(f'{n}{list(v.shape)}' for n, v in arrays.items())} to {out_dir}")
+    return {n: list(v.shape) for n, v in arrays.items()}
+
+
 def launch_ranks(a) -> int:
     """`python bench.py --gpus N` (N > 1) outside a launcher: start N ranks under
     torch.distributed.run as a CHILD process (this parent never imports torch or touches a GPU, and
@@ -555,7 +601,14 @@ def main() -> int:
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--layout", choices=["auto", "fused", "split"], default="auto",
                     help="graph layout (A/B; auto picks by gather-space size)")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the oracle leg (no cpu_baseline, no parity)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the validation leg: parity against the oracle (every "
+                         "exchange mode when N > 1) and the cpu_baseline; a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed as DIR/<name>.npy (float64): "
+                         "ranks (a fixed seeded sample above 2^21 vertices), ranks_index, stats")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the oracle leg (no cpu_baseline, no parity)")
     ap.add_argument("--parity-iters", type=int, default=10, help="K of the parity / cpu_baseline leg (Sparky.java:187)")
     ap.add_argument("--no-overlap-ab", action="store_true",
                     help="N > 1: skip the exchange-mode calibration and time the library default")
@@ -589,7 +642,8 @@ def main() -> int:
         if rank == 0:
             print(json.dumps(contract_error_line(a.gpus, a.steps, a.warmup, msg)), flush=True)
         return 2
-    limits = {"init": 300, "generate": 300, "build": 600, "attach": 180, "calibration": 600, "timed": 600, "parity": 900}
+    limits = {"init": 300, "generate": 300, "build": 600, "attach": 180, "calibration": 600, "timed": 600, "dump": 300,
+              "parity": 900}
     if a.stage_timeout is not None:
         limits = {k: a.stage_timeout for k in limits}
     wd = Watchdog(rank, world, a.steps, a.warmup)
@@ -628,7 +682,7 @@ def main() -> int:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", dev))
 
-    validate = not a.no_cpu_baseline
+    validate = a.full and not a.no_cpu_baseline
     bopts = {k: int(v) for k, v in (o.split("=", 1) for o in a.build_option)}
 
     raw = []  # rank 0 with validation: a host copy of the raw interned edges for the oracle's own CSR build
@@ -728,10 +782,15 @@ def main() -> int:
 
     tr = pmc_traffic(workload) if world == 1 else None
 
-    # ---- validation leg (after the timed region): K iterations from a fresh reset vs the oracle ----
+    dumped = None
+    if a.dump_outputs:
+        wd.enter("dump", limits["dump"])
+        dumped = dump_outputs(a.dump_outputs, g, dist, rank, V, st)
+
+    # ---- validation leg (--full, after the timed region): K iterations from a fresh reset vs the oracle ----
     cpu, parity = None, None
-    wd.enter("parity", limits["parity"])
     if validate:
+        wd.enter("parity", limits["parity"])
         K = a.parity_iters
 
         mine, owned_once, checked, failed = parity_runs(g, dist, rank, V, K, mode, ipc_ok, overlap is not None)
@@ -809,6 +868,8 @@ def main() -> int:
             "vs_baseline": None,
             "dtype": "f64",
             "data": "synthetic (seeded device-side generator; no dataset)",
+            "full": bool(a.full),
+            "outputs": dumped,
             "config": {
                 "workload": workload,
                 "n_vertices": V,

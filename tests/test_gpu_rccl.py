@@ -35,7 +35,7 @@ def _run(world, extra, scale=20, timeout=280, launcher=True, steps=6, warmup=2, 
     if launcher:
         cmd += ["-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
                 f"--master-port={_free_port()}"]
-    cmd += [os.path.join(ROOT, "bench.py"), "--gpus", str(world)] + (["--share-device"] if share else []) + [
+    cmd += [os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(world)] + (["--share-device"] if share else []) + [
             "--scale", str(scale), "--steps",
             str(steps), "--warmup", str(warmup), "--parity-iters", "10", "--stage-timeout", "150"] + extra
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}

@@ -7,7 +7,7 @@
 #   pytest            python -m pytest tests -m gpu (everything, -x, per-test timeout)
 #   pytest:<expr>     the same restricted with -k <expr> ('+' between names: ' or ')
 #   smoke             __graft_entry__.smoke()
-#   bench[:args]      python bench.py <args, ',' for ' '>        (log: bench_<n>.log)
+#   bench[:args]      python bench.py --full <args, ',' for ' '> (log: <n>_bench.log)
 #   trace[:args]      rocprofv3 --kernel-trace --stats on bench.py --no-cpu-baseline <args>
 #   pmc[:args]        FETCH_SIZE, WRITE_SIZE and TCC hit/miss passes (one counter set per run,
 #                     never combined with trace domains) + tools/pmc_summary.py
@@ -16,7 +16,7 @@
 #   py:<args>         python <args> (a tool script)
 #   pmcpy:<c>:<args>  one rocprofv3 --pmc <c> pass over python <args> (a tool script)
 #   tracepy:<args>    rocprofv3 --kernel-trace --memory-copy-trace --stats -- python3 <args>
-#   dist:<N>:<args>   bench.py --gpus N --share-device <args> under torch.distributed.run (N ranks
+#   dist:<N>:<args>   bench.py --full --gpus N --share-device <args> under torch.distributed.run (N ranks
 #                     sharing the box's GPU; RCCL over loopback sockets: the N > 1 path for real)
 # Environment variables may prefix a step as KEY=VAL@step (e.g. PR_LIB_PATH=... for an A/B build;
 # the library itself reads no environment: layout choices are bench.py options).
@@ -41,7 +41,7 @@ for step in "$@"; do
     smoke)
       env "${envs[@]}" timeout -k 10 120 python -u -c "import __graft_entry__ as g; g.smoke()" > $log 2>&1 || exit 1 ;;
     bench)
-      env "${envs[@]}" timeout -k 10 400 python -u bench.py $args > $log 2>&1 || exit 1 ;;
+      env "${envs[@]}" timeout -k 10 400 python -u bench.py --full $args > $log 2>&1 || exit 1 ;;
     trace)
       env "${envs[@]}" timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$n -o run -- python3 bench.py --no-cpu-baseline --steps 10 $args > $log 2>&1 || exit 1 ;;
     pmc)
@@ -64,7 +64,7 @@ for step in "$@"; do
     dist)
       N=${arg%%:*}; rest=${arg#*:}; [ "$rest" = "$arg" ] && rest=""
       env "${envs[@]}" timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N \
-        --master-addr 127.0.0.1 --master-port $((29500 + n)) bench.py --gpus $N --share-device ${rest//,/ } > $log 2>&1 || exit 1 ;;
+        --master-addr 127.0.0.1 --master-port $((29500 + n)) bench.py --full --gpus $N --share-device ${rest//,/ } > $log 2>&1 || exit 1 ;;
     *)
       echo "unknown step $name" >&2; exit 2 ;;
   esac

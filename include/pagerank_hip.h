@@ -174,6 +174,26 @@ int pr_reset(pr_graph *g, double teleport, double damping, const double *init_ra
 int pr_step(pr_graph *g, int32_t iterations);
 int pr_sync(pr_graph *g);
 int pr_get_ranks(pr_graph *g, double *ranks_out);
+
+/* Top-K query, selected on the device: the k highest-ranked vertices of this part (the rows it
+ * owns; with one part, of the graph), rank descending, ties broken by original vertex ID
+ * ascending.  Ranks compare by the order-preserving map of their IEEE-754 bits to a u64 (sign bit
+ * set for a non-negative value, all bits inverted for a negative one: any finite or infinite
+ * double works, -0.0 sorts just below +0.0; a NaN's position is unspecified).  Ties are exact: when
+ * the k-th vertex falls inside a class of bit-identical ranks, the lowest IDs of that class are
+ * returned.  Writes n = min(k, rows owned) pairs to ids_out / ranks_out (caller-allocated, k
+ * entries each) and n to *n_out; the ranks are the bits pr_get_ranks returns for those IDs.  Only K
+ * pairs cross to the host (pr_get_ranks copies and scatters all V).  Like pr_get_ranks the call
+ * waits for the enqueued steps.  k < 0 or a NULL pointer: PR_ERR_INVALID; before pr_reset:
+ * PR_ERR_STATE; k == 0: PR_OK with *n_out = 0.  The first call uploads the row -> original ID map
+ * and allocates scratch (4 bytes per row + 12 per candidate and selected pair; PR_INFO_DEVICE_BYTES
+ * counts them from then on); graphs that never ask pay nothing. */
+int pr_get_topk(pr_graph *g, int32_t k, int32_t *ids_out, double *ranks_out, int32_t *n_out);
+/* Pure host, needs no GPU: merges n_lists lists that are already in top-K order into the k best
+ * (n = min(k, total entries)).  For one process per GPU (RCCL): every rank calls pr_get_topk on
+ * its part and the host merges the lists it collects.  counts[l] entries in ids[l] / ranks[l]. */
+int pr_topk_merge(int32_t n_lists, const int32_t *const *ids, const double *const *ranks,
+                  const int32_t *counts, int32_t k, int32_t *ids_out, double *ranks_out, int32_t *n_out);
 int pr_set_timing(pr_graph *g, int32_t enable);
 int pr_get_stats(pr_graph *g, double *stats, int32_t n_stats);
 
@@ -220,6 +240,9 @@ int pr_group_reset(pr_graph *const *parts, int32_t n_parts, double teleport, dou
                    const double *init_ranks);
 int pr_group_step(pr_graph *const *parts, int32_t n_parts, int32_t iterations);
 int pr_group_sync(pr_graph *const *parts, int32_t n_parts);
+/* pr_get_topk over a single-process group: every part's list, merged (pr_topk_merge). */
+int pr_group_topk(pr_graph *const *parts, int32_t n_parts, int32_t k, int32_t *ids_out,
+                  double *ranks_out, int32_t *n_out);
 
 void pr_graph_destroy(pr_graph *g);
 

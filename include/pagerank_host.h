@@ -44,6 +44,10 @@ int32_t prh_java_double(double x, char *buf);
 int prh_write_part(const prh_edges *e, const char *dir, int32_t iter, const double *ranks);
 /* "<url> has rank: <r>." for every URL, to path (NULL = stdout). */
 int prh_write_has_rank(const prh_edges *e, const char *path, const double *ranks);
+/* "<url> has rank: <r>." for ids[0..n) in that order (a top-K list: pr_get_topk's ids / ranks),
+   to path (NULL = stdout).  An ID outside [0, n_vertices) fails before anything is written. */
+int prh_write_has_rank_ids(const prh_edges *e, const char *path, const int32_t *ids,
+                           const double *ranks, int32_t n);
 /* Resume: ranks[id] from the "(url,rank)" lines of every dir/part-* file (a PageRank<i>
    directory written by prh_write_part or by Sparky.java:237's saveAsTextFile).  Every URL of
    the edge list must appear exactly once, and only those. */

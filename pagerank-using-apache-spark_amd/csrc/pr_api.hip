@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "pr_graph.h"
+#include "pr_topk.h"
 #include "pr_xcheck.h"
 
 namespace pr {
@@ -48,6 +49,7 @@ size_t pr_graph::device_bytes() const {
   b += rowptr.bytes + col.bytes + colp.bytes + rowinfo.bytes + colh.bytes + hunits.bytes + partial.bytes + poff.bytes + rmask.bytes + cbase.bytes + seg_slot.bytes + seg_p0.bytes + r.bytes + cbuf[0].bytes + cbuf[1].bytes + eoff.bytes + epos.bytes;
   b += units.bytes + unit_part.bytes + lr_row.bytes + lr_p0.bytes + piece_part.bytes;
   b += fin_part.bytes + fin_counter.bytes + reset_part.bytes + x_send.bytes + x_sbuf.bytes + hpos.bytes + cside.bytes;
+  b += pr::topk_bytes(this);  // 0 until the first pr_get_topk
   return b;
 }
 
@@ -529,6 +531,94 @@ int pr_group_sync(pr_graph *const *parts, int32_t n_parts) {
   return PR_OK;
 }
 
+static int topk_args(int32_t k, const int32_t *ids_out, const double *ranks_out, const int32_t *n_out) {
+  if (k < 0) return fail(PR_ERR_INVALID, "k < 0");
+  if (!n_out || (k > 0 && (!ids_out || !ranks_out))) return fail(PR_ERR_INVALID, "NULL argument");
+  return PR_OK;
+}
+
+int pr_get_topk(pr_graph *g, int32_t k, int32_t *ids_out, double *ranks_out, int32_t *n_out) {
+  if (!g) return fail(PR_ERR_INVALID, "NULL graph");
+  PR_TRY(topk_args(k, ids_out, ranks_out, n_out));
+  if (!g->ready) return fail(PR_ERR_STATE, "pr_get_topk before pr_reset");
+  DeviceGuard dg(g->device);
+  return pr::topk_part(g, k, pr::kTopkNarrowDiv, ids_out, ranks_out, n_out, nullptr);
+}
+
+// Internal entry point (not part of include/pagerank_hip.h): pr_get_topk with the narrowing
+// threshold as a parameter (candidates are compacted once they are <= n_rows / narrow_div; 0:
+// never) and the pass counts in info[4] (pr_graph.h topk_part), so that tests reach both sides
+// of the switch at small sizes.
+int pr_topk_select_ex(pr_graph *g, int32_t k, int64_t narrow_div, int32_t *ids_out, double *ranks_out,
+                      int32_t *n_out, int32_t *info) {
+  if (!g) return fail(PR_ERR_INVALID, "NULL graph");
+  PR_TRY(topk_args(k, ids_out, ranks_out, n_out));
+  if (narrow_div < 0) return fail(PR_ERR_INVALID, "narrow_div < 0");
+  if (!g->ready) return fail(PR_ERR_STATE, "pr_get_topk before pr_reset");
+  DeviceGuard dg(g->device);
+  return pr::topk_part(g, k, narrow_div, ids_out, ranks_out, n_out, info);
+}
+
+int pr_topk_merge(int32_t n_lists, const int32_t *const *ids, const double *const *ranks, const int32_t *counts,
+                  int32_t k, int32_t *ids_out, double *ranks_out, int32_t *n_out) {
+  if (n_lists < 0) return fail(PR_ERR_INVALID, "n_lists < 0");
+  PR_TRY(topk_args(k, ids_out, ranks_out, n_out));
+  if (n_lists > 0 && (!ids || !ranks || !counts)) return fail(PR_ERR_INVALID, "NULL argument");
+  for (int32_t l = 0; l < n_lists; ++l) {
+    if (counts[l] < 0) return fail(PR_ERR_INVALID, "negative list length");
+    if (counts[l] > 0 && (!ids[l] || !ranks[l])) return fail(PR_ERR_INVALID, "NULL list");
+  }
+  auto head = [&](int32_t l, int32_t i) {
+    uint64_t bits;
+    std::memcpy(&bits, &ranks[l][i], sizeof(bits));
+    return pr::TopkPair{pr::topk_rank_key(bits), ids[l][i]};
+  };
+  std::vector<int32_t> at((size_t)n_lists, 0);
+  int32_t n = 0;
+  for (; n < k; ++n) {  // the best head of the lists, k times
+    int32_t best = -1;
+    pr::TopkPair bp{0, 0};
+    for (int32_t l = 0; l < n_lists; ++l) {
+      if (at[l] >= counts[l]) continue;
+      const pr::TopkPair h = head(l, at[l]);
+      if (best < 0 || pr::topk_before(h, bp)) {
+        best = l;
+        bp = h;
+      }
+    }
+    if (best < 0) break;
+    ids_out[n] = ids[best][at[best]];
+    ranks_out[n] = ranks[best][at[best]];
+    ++at[best];
+  }
+  *n_out = n;
+  return PR_OK;
+}
+
+int pr_group_topk(pr_graph *const *parts, int32_t n_parts, int32_t k, int32_t *ids_out, double *ranks_out,
+                  int32_t *n_out) {
+  PR_TRY(check_group(parts, n_parts));
+  PR_TRY(topk_args(k, ids_out, ranks_out, n_out));
+  for (int32_t p = 0; p < n_parts; ++p)
+    if (!parts[p]->ready) return fail(PR_ERR_STATE, "pr_group_topk before pr_group_reset");
+  std::vector<std::vector<int32_t>> lid((size_t)n_parts);
+  std::vector<std::vector<double>> lrk((size_t)n_parts);
+  std::vector<const int32_t *> pid((size_t)n_parts);
+  std::vector<const double *> prk((size_t)n_parts);
+  std::vector<int32_t> cnt((size_t)n_parts, 0);
+  for (int32_t p = 0; p < n_parts; ++p) {
+    pr_graph *g = parts[p];
+    const size_t m = (size_t)std::min<int64_t>(k, g->n_local);
+    lid[p].resize(m + 1);
+    lrk[p].resize(m + 1);
+    DeviceGuard dg(g->device);
+    PR_TRY(pr::topk_part(g, k, pr::kTopkNarrowDiv, lid[p].data(), lrk[p].data(), &cnt[p], nullptr));
+    pid[p] = lid[p].data();
+    prk[p] = lrk[p].data();
+  }
+  return pr_topk_merge(n_parts, pid.data(), prk.data(), cnt.data(), k, ids_out, ranks_out, n_out);
+}
+
 void pr_graph_destroy(pr_graph *g) {
   if (!g) return;
   DeviceGuard dg(g->device);
@@ -547,6 +637,7 @@ void pr_graph_destroy(pr_graph *g) {
   if (g->stream) (void)hipStreamSynchronize(g->stream);
   if (g->xstream) (void)hipStreamSynchronize(g->xstream);
   pr::ipc_destroy(g);  // after the peers' last copies out of this part's send runs
+  pr::topk_destroy(g);
   if (g->comm) (void)ncclCommDestroy(g->comm);
   for (hipEvent_t e : g->ev_pool) (void)hipEventDestroy(e);
   if (g->xev) (void)hipEventDestroy(g->xev);

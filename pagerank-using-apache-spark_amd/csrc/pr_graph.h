@@ -33,6 +33,7 @@
 
 namespace pr {
 struct IpcState;  // pr_ipc.hip
+struct TopkState;  // pr_topk.hip
 }
 
 // Build options (include/pagerank_hip.h PR_BOPT_*): the library reads no environment variables.
@@ -201,6 +202,10 @@ struct pr_graph {
   bool grouped = false;
   hipEvent_t xev = nullptr;
 
+  // top-K query (pr_topk.hip): the device copy of orig_of_local and the select's scratch, allocated
+  // by the first pr_get_topk and kept until destroy (nullptr: never asked)
+  pr::TopkState *topk = nullptr;
+
   size_t device_bytes() const;
 };
 
@@ -246,4 +251,14 @@ void ipc_destroy(pr_graph *g);
 bool stream_idle_within(hipStream_t s, double seconds);  // host poll of hipStreamQuery with a deadline
 hipEvent_t next_event(pr_graph *g);  // the next timing event of g's pool (nullptr: creation failed)
 int time_mark(pr_graph *g, hipStream_t s, int *index);  // records one on s; *index into ev_pool
+// Top-K query (pr_topk.hip): the n = min(k, rows owned) best (original ID, rank) pairs of this part
+// in the query's order; waits for g's enqueued work first.  narrow_div: the candidates are
+// compacted once they are at most n_rows / narrow_div (0: never).  info (may be NULL): {histogram
+// passes, those over the rows, those over the compacted candidates, digits known when the
+// candidates were compacted or -1}.
+constexpr int64_t kTopkNarrowDiv = 8;
+int topk_part(pr_graph *g, int64_t k, int64_t narrow_div, int32_t *ids_out, double *ranks_out, int32_t *n_out,
+              int32_t *info);
+size_t topk_bytes(const pr_graph *g);  // device memory the query holds (0 before the first call)
+void topk_destroy(pr_graph *g);
 }  // namespace pr

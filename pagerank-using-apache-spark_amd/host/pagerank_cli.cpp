@@ -2,7 +2,7 @@
 //
 //   pagerank <input-path> [iterations=10] [--format=edges|ccjson] [--out DIR]
 //            [--save-every-iter] [--dangling=local|none] [--device N] [--quiet] [--stats]
-//            [--resume DIR/PageRank<i>] [--devices D0,D1,...]
+//            [--resume DIR/PageRank<i>] [--devices D0,D1,...] [--top K]
 //
 // Input (libpagerank_host): "src dst" edge list ("src" alone = record without links), or
 // --format=ccjson "url<TAB>json" Common Crawl metadata records (Sparky.java:61-123).  URLs are
@@ -18,6 +18,9 @@
 // --devices D0,D1,...: one row part per listed GPU (a device may repeat), driven from this one
 // process by the pr_group_* API; the parts exchange contributions by device copies (xGMI peer
 // copies between GPUs).  Same outputs as one GPU.
+// --top K: the final listing is only the K highest-ranked URLs, rank descending, ties by first
+// appearance in the input (= ID ascending), selected on the GPU (pr_get_topk / pr_group_topk).
+// Without --out the rank vector never crosses to the host; --out still writes complete part files.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -36,6 +39,7 @@ struct Options {
   bool save_every = false, quiet = false, stats = false;
   uint32_t flags = PR_DANGLING_LOCAL;
   int device = 0;
+  int top = 0;  // --top K (0: list every URL)
   std::vector<int> devices;  // --devices: one part per entry (empty: one part on `device`)
 };
 
@@ -58,7 +62,7 @@ std::vector<int> parse_devices(const std::string &s) {
   std::fprintf(stderr,
                "usage: pagerank <input-path> [iterations=10] [--format=edges|ccjson] [--out DIR]\n"
                "                [--save-every-iter] [--dangling=local|none] [--device N] [--quiet] [--stats]\n"
-               "                [--resume DIR/PageRank<i>] [--devices D0,D1,...]\n");
+               "                [--resume DIR/PageRank<i>] [--devices D0,D1,...] [--top K]\n");
   std::exit(2);
 }
 
@@ -82,6 +86,12 @@ Options parse(int argc, char **argv) {
     else if ((a == "--devices" && i + 1 < argc) || a.rfind("--devices=", 0) == 0) {
       o.devices = parse_devices(a == "--devices" ? std::string(argv[++i]) : a.substr(10));
       if (o.devices.empty()) usage("--devices takes a comma-separated list of device numbers");
+    }
+    else if ((a == "--top" && i + 1 < argc) || a.rfind("--top=", 0) == 0) {
+      const std::string t = a == "--top" ? std::string(argv[++i]) : a.substr(6);
+      if (t.empty() || t.size() > 9 || t.find_first_not_of("0123456789") != std::string::npos || std::atoi(t.c_str()) < 1)
+        usage("--top takes a count K >= 1");
+      o.top = std::atoi(t.c_str());
     }
     else if (a == "-h" || a == "--help") usage(nullptr);
     else if (!a.empty() && a[0] == '-') usage(("unknown option " + a).c_str());
@@ -131,7 +141,7 @@ void on_iter(int32_t it_run, const double *ranks, double dc, double l1, double m
 // the same callback protocol as pr_run (ranks merged from every part, dc / L1 from part 0's
 // stats, which sum every part's slots).
 int run_group(const Options &o, const prh_edges *edges, const double *init, int n_run, Job *job,
-              std::vector<double> *ranks) {
+              std::vector<double> *ranks, std::vector<int32_t> *top_ids, std::vector<double> *top_ranks) {
   const int P = (int)o.devices.size();
   const int32_t V = prh_n_vertices(edges);
   std::vector<pr_graph *> parts(P, nullptr);
@@ -153,7 +163,13 @@ int run_group(const Options &o, const prh_edges *edges, const double *init, int 
     for (int p = 0; p < P && rc == PR_OK && fetch; ++p) rc = pr_get_ranks(parts[p], ranks->data());
     if (rc == PR_OK) on_iter(it, fetch ? ranks->data() : nullptr, st[PR_STAT_LAST_DC], st[PR_STAT_LAST_L1], ms, job);
   }
-  for (int p = 0; p < P && rc == PR_OK; ++p) rc = pr_get_ranks(parts[p], ranks->data());
+  // --top: the K best pairs instead of the whole vector (which no part file needs any more here)
+  for (int p = 0; p < P && rc == PR_OK && o.top == 0; ++p) rc = pr_get_ranks(parts[p], ranks->data());
+  if (rc == PR_OK && o.top > 0 && !o.quiet) {
+    int32_t n = 0;
+    rc = pr_group_topk(parts.data(), P, (int32_t)top_ids->size(), top_ids->data(), top_ranks->data(), &n);
+    top_ids->resize(rc == PR_OK ? (size_t)n : 0);
+  }
   const std::string err = rc == PR_OK ? std::string() : std::string(pr_last_error());
   for (pr_graph *g : parts)
     if (g) pr_graph_destroy(g);
@@ -179,6 +195,9 @@ int main(int argc, char **argv) {
   double ms_build = 0.0, ms_run = 0.0;
   Job job{&o, edges};
   std::vector<double> ranks((size_t)V + 1), init;
+  const int32_t top_k = o.top < V ? o.top : V;  // --top: K pairs at most, never more than the URLs
+  std::vector<int32_t> top_ids((size_t)top_k);
+  std::vector<double> top_ranks((size_t)top_k);
   if (!o.resume.empty()) {
     init.assign((size_t)V + 1, 0.0);
     if (prh_read_ranks(edges, o.resume.c_str(), init.data()) != 0) {
@@ -193,7 +212,7 @@ int main(int argc, char **argv) {
   if (o.devices.size() > 1) {
     if (n_run > 0) std::printf("Starting iter%d\n", job.start);
     const auto t0 = Clock::now();
-    if (run_group(o, edges, init_p, n_run, &job, &ranks) != PR_OK) {
+    if (run_group(o, edges, init_p, n_run, &job, &ranks, &top_ids, &top_ranks) != PR_OK) {
       prh_free(edges);
       return 1;
     }
@@ -213,8 +232,15 @@ int main(int argc, char **argv) {
     t0 = Clock::now();
     // ranks cross PCIe only for the part files that are written: every iteration's with
     // --save-every-iter, else only the last one's, which pr_run returns in `ranks` anyway
+    // (with --top and no --out not at all: the listing's K pairs come from pr_get_topk)
     const bool every = !o.out.empty() && o.save_every;
-    rc = pr_run(g, n_run, 0.15, 0.85, init_p, ranks.data(), on_iter, every ? PR_CB_RANKS : 0u, &job);
+    double *final_ranks = o.top > 0 && o.out.empty() ? nullptr : ranks.data();
+    rc = pr_run(g, n_run, 0.15, 0.85, init_p, final_ranks, on_iter, every ? PR_CB_RANKS : 0u, &job);
+    if (rc == PR_OK && o.top > 0 && !o.quiet) {
+      int32_t n = 0;
+      rc = pr_get_topk(g, top_k, top_ids.data(), top_ranks.data(), &n);
+      top_ids.resize(rc == PR_OK ? (size_t)n : 0);
+    }
     if (rc == PR_OK && !o.out.empty() && !every && n_run > 0 &&
         prh_write_part(edges, o.out.c_str(), o.iterations - 1, ranks.data()) != 0) {
       std::fprintf(stderr, "pagerank: %s\n", prh_last_error());
@@ -230,7 +256,10 @@ int main(int argc, char **argv) {
   }
   std::fflush(stdout);
   const auto t_out = Clock::now();
-  if (!o.quiet && prh_write_has_rank(edges, nullptr, ranks.data()) != 0) {
+  const int rc_out = o.quiet   ? 0
+                     : o.top > 0 ? prh_write_has_rank_ids(edges, nullptr, top_ids.data(), top_ranks.data(), (int32_t)top_ids.size())
+                                 : prh_write_has_rank(edges, nullptr, ranks.data());
+  if (rc_out != 0) {
     std::fprintf(stderr, "pagerank: %s\n", prh_last_error());
     job.error = 1;
   }

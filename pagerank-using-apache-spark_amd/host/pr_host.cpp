@@ -884,6 +884,32 @@ int prh_write_has_rank(const prh_edges *e, const char *path, const double *ranks
   return rc;
 }
 
+int prh_write_has_rank_ids(const prh_edges *e, const char *path, const int32_t *ids, const double *ranks, int32_t n) {
+  if (!e || n < 0 || (n > 0 && (!ids || !ranks))) return fail("bad argument");
+  for (int32_t i = 0; i < n; ++i)
+    if (ids[i] < 0 || (size_t)ids[i] >= e->names.size()) return fail("URL id " + std::to_string(ids[i]) + " out of range");
+  FILE *f = path ? std::fopen(path, "w") : stdout;
+  if (!f) return fail(std::string("cannot write ") + path);
+  char num[64];
+  std::string buf;
+  for (int32_t i = 0; i < n; ++i) {
+    buf.append(e->names[(size_t)ids[i]]);
+    buf.append(" has rank: ");
+    buf.append(num, pr_host::java_double_to_string(ranks[i], num));
+    buf.append(".\n");
+    if (buf.size() > (1 << 20) - 8192 || i + 1 == n) {
+      if (std::fwrite(buf.data(), 1, buf.size(), f) != buf.size()) {
+        if (path) std::fclose(f);
+        return fail("write failed");
+      }
+      buf.clear();
+    }
+  }
+  if (path) std::fclose(f);
+  else std::fflush(f);
+  return 0;
+}
+
 // Resume: the "(url,rank)" lines of every part-* file of a saveAsTextFile
 // directory (Sparky.java:237), mapped through the interned names.  Every URL of the edge list
 // must appear exactly once and no other URL may; the rank is the text Double.toString wrote

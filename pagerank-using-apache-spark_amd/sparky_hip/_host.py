@@ -46,6 +46,7 @@ def load() -> ctypes.CDLL:
         L.prh_java_double.restype = ctypes.c_int32
         L.prh_write_part.argtypes = [P, ctypes.c_char_p, ctypes.c_int32, P]
         L.prh_write_has_rank.argtypes = [P, ctypes.c_char_p, P]
+        L.prh_write_has_rank_ids.argtypes = [P, ctypes.c_char_p, P, P, ctypes.c_int32]
         L.prh_read_ranks.argtypes = [P, ctypes.c_char_p, P]
         L.prh_free.argtypes = [P]
         L.prh_free.restype = None
@@ -108,6 +109,16 @@ class HostEdges:
         r = np.ascontiguousarray(ranks, dtype=np.float64)
         _check(load().prh_write_has_rank(self._h, path.encode() if path else None,
                                          r.ctypes.data_as(ctypes.c_void_p)))
+
+    def write_has_rank_ids(self, path: Optional[str], ids: np.ndarray, ranks: np.ndarray) -> None:
+        """``<url> has rank: <r>.`` for the given IDs in the given order (a top-K list)."""
+        i = np.ascontiguousarray(ids, dtype=np.int32)
+        r = np.ascontiguousarray(ranks, dtype=np.float64)
+        if i.shape != r.shape or i.ndim != 1:
+            raise ValueError("ids and ranks must be 1-D arrays of the same length")
+        _check(load().prh_write_has_rank_ids(self._h, path.encode() if path else None,
+                                             i.ctypes.data_as(ctypes.c_void_p), r.ctypes.data_as(ctypes.c_void_p),
+                                             int(i.shape[0])))
 
     def read_ranks(self, directory: str) -> np.ndarray:
         """Resume input: the saved ``(url,rank)`` lines of ``directory/part-*`` in ID order."""

@@ -2,7 +2,7 @@
 
 CLI: ``python -m sparky_hip <input-path> [iterations=10] [--format edges|ccjson]
 [--out DIR] [--save-every-iter] [--dangling=local|none] [--device N] [--quiet]
-[--resume DIR/PageRank<i>]``
+[--resume DIR/PageRank<i>] [--devices D0,D1,...] [--top K]``
 
 * input: text edge list, ``src dst`` per line; a single-token line ``src`` is a record without
   ``a`` links (Sparky.java:114-118).  Tokens (URLs) are taken verbatim and interned to dense
@@ -16,6 +16,9 @@ CLI: ``python -m sparky_hip <input-path> [iterations=10] [--form
 * ``--resume DIR/PageRank<i>``: start from the ranks saved there (instead of 1.0,
   Sparky.java:165-170) and continue the same loop with iterations i+1 .. N-1 (a directory not
   named ``PageRank<i>`` starts the loop at 0).  Same rules as the C++ CLI.
+* ``--top K``: the final listing is only the K highest-ranked URLs -- rank descending, ties by
+  first appearance (ID ascending) -- selected on the GPU (``PageRankGraph.topk`` /
+  ``PartGroup.topk``); without ``--out`` the rank vector never crosses to the host.
 """
 from __future__ import annotations
 
@@ -133,9 +136,10 @@ def saved_iteration(path: str) -> int:
     return -1
 
 
-def _run_group(edges, devices, dangling, n_run, init, cb, want_ranks):
+def _run_group(edges, devices, dangling, n_run, init, cb, want_ranks, top=0):
     """--devices: one part per listed device, one process (pr_group_*); the callback gets the
-    merged ranks of every part after each iteration, as with PageRankGraph.run."""
+    merged ranks of every part after each iteration, as with PageRankGraph.run.  Returns the
+    final ranks, or with top > 0 the (ids, ranks) of PartGroup.topk(top)."""
     P = len(devices)
     parts = []
     try:
@@ -148,7 +152,7 @@ def _run_group(edges, devices, dangling, n_run, init, cb, want_ranks):
             grp.step(1)
             grp.sync()
             cb(it, grp.ranks() if want_ranks else None, None)
-        return grp.ranks()
+        return grp.topk(top) if top > 0 else grp.ranks()
     finally:
         for g in parts:
             g.close()
@@ -169,7 +173,12 @@ def main(argv=None) -> int:
     ap.add_argument("--resume", default=None, metavar="DIR", help="start from saved (url,rank) part files")
     ap.add_argument("--devices", default=None, metavar="D0,D1,...",
                     help="one row part per listed GPU (a device may repeat), one process (pr_group_*)")
+    ap.add_argument("--top", type=int, default=None, metavar="K",
+                    help="list only the K highest-ranked URLs (selected on the GPU)")
     a = ap.parse_args(argv)
+    if a.top is not None and a.top < 1:
+        ap.error("--top takes a count K >= 1")
+    top = a.top or 0
     devices = [a.device]
     if a.devices is not None:
         try:
@@ -197,11 +206,21 @@ def main(argv=None) -> int:
     if len(devices) == 1:
         with PageRankGraph(edges.n_vertices, edges.src, edges.dst, device=devices[0], dangling=a.dangling,
                            keep_canonical=False) as g:
-            ranks, _ = g.run(n_run, callback=cb, want_ranks_in_callback=bool(a.out), init_ranks=init)
+            if top and not a.out:  # no part file: the ranks stay on the device
+                g.reset(init_ranks=init)
+                for it in range(n_run):
+                    g.step(1)
+                    cb(it, None, None)
+            else:
+                ranks, _ = g.run(n_run, callback=cb, want_ranks_in_callback=bool(a.out), init_ranks=init)
+            if top:
+                ranks = g.topk(top)
     else:
-        ranks = _run_group(edges, devices, a.dangling, n_run, init, cb, bool(a.out))
+        ranks = _run_group(edges, devices, a.dangling, n_run, init, cb, bool(a.out), top)
     out.flush()
-    if not a.quiet:
+    if not a.quiet and top:
+        edges.write_has_rank_ids(None, *ranks)
+    elif not a.quiet:
         edges.write_has_rank(None, ranks)
     edges.close()
     return 0

@@ -202,6 +202,30 @@ class PageRankGraph:
         check(_lib.load().pr_get_ranks(self._h, _ptr(out)))
         return out[: self.n_vertices]
 
+    def topk(self, k: int):
+        """pr_get_topk: the k highest-ranked vertices of this part, selected on the device -- rank
+        descending, ties by original ID ascending.  Returns (ids int32[n], ranks float64[n]) with
+        n = min(k, rows owned); only those pairs cross to the host."""
+        k = int(k)
+        ids, rk = np.zeros(max(k, 1), np.int32), np.zeros(max(k, 1), np.float64)
+        n = ctypes.c_int32(0)
+        check(_lib.load().pr_get_topk(self._h, k, _ptr(ids), _ptr(rk), ctypes.byref(n)))
+        return ids[: n.value], rk[: n.value]
+
+    def _topk_ex(self, k: int, narrow_div: int):
+        """The library's internal entry point behind topk(): the same query with the narrowing
+        threshold as a parameter (candidates are compacted once they are <= rows / narrow_div; 0:
+        never).  Returns (ids, ranks, info) with info = {passes, row_passes, cand_passes,
+        narrowed_at}.  For tests and tools/topk_bench.py."""
+        k = int(k)
+        ids, rk = np.zeros(max(k, 1), np.int32), np.zeros(max(k, 1), np.float64)
+        n = ctypes.c_int32(0)
+        info = np.zeros(4, np.int32)
+        check(_lib.load().pr_topk_select_ex(self._h, k, int(narrow_div), _ptr(ids), _ptr(rk), ctypes.byref(n),
+                                            _ptr(info)))
+        return ids[: n.value], rk[: n.value], dict(zip(("passes", "row_passes", "cand_passes", "narrowed_at"),
+                                                       (int(x) for x in info)))
+
     def set_timing(self, enable: bool) -> None:
         check(_lib.load().pr_set_timing(self._h, 1 if enable else 0))
 
@@ -235,6 +259,24 @@ class PageRankGraph:
     def attach_comm(self, rank: int, n_ranks: int, uid: bytes) -> None:
         buf = (ctypes.c_uint8 * _lib.PR_COMM_ID_BYTES).from_buffer_copy(uid)
         check(_lib.load().pr_graph_attach_comm(self._h, rank, n_ranks, buf))
+
+
+def merge_topk(lists, k: int):
+    """pr_topk_merge (pure host): merges (ids, ranks) lists that are each in top-K order -- one per
+    part or per RCCL rank -- into the k best.  Returns (ids int32[n], ranks float64[n])."""
+    k = int(k)
+    lists = [(np.ascontiguousarray(i, dtype=np.int32), np.ascontiguousarray(r, dtype=np.float64)) for i, r in lists]
+    for i, r in lists:
+        if i.shape != r.shape or i.ndim != 1:
+            raise ValueError("every list is a pair of 1-D arrays of the same length")
+    n_l = len(lists)
+    pid = (ctypes.c_void_p * max(n_l, 1))(*[i.ctypes.data for i, _ in lists])
+    prk = (ctypes.c_void_p * max(n_l, 1))(*[r.ctypes.data for _, r in lists])
+    cnt = np.array([i.shape[0] for i, _ in lists] or [0], np.int32)
+    ids, rk = np.zeros(max(k, 1), np.int32), np.zeros(max(k, 1), np.float64)
+    n = ctypes.c_int32(0)
+    check(_lib.load().pr_topk_merge(n_l, pid, prk, _ptr(cnt), k, _ptr(ids), _ptr(rk), ctypes.byref(n)))
+    return ids[: n.value], rk[: n.value]
 
 
 def comm_unique_id() -> bytes:
@@ -304,6 +346,14 @@ class PartGroup:
         for p in self.parts:
             p.ranks(out)
         return out[:V]
+
+    def topk(self, k: int):
+        """pr_group_topk: every part's top-K list, merged; (ids int32[n], ranks float64[n])."""
+        k = int(k)
+        ids, rk = np.zeros(max(k, 1), np.int32), np.zeros(max(k, 1), np.float64)
+        n = ctypes.c_int32(0)
+        check(_lib.load().pr_group_topk(self._arr, len(self.parts), k, _ptr(ids), _ptr(rk), ctypes.byref(n)))
+        return ids[: n.value], rk[: n.value]
 
     def run(self, iterations: int, **kw) -> np.ndarray:
         self.reset(**kw)

@@ -175,6 +175,31 @@ int pr_step(pr_graph *g, int32_t iterations);
 int pr_sync(pr_graph *g);
 int pr_get_ranks(pr_graph *g, double *ranks_out);
 
+/* Personalised (topic-sensitive) PageRank: a per-vertex teleport vector t in the scalar's place.
+ * With a vector set, one iteration is r'[v] = t[v] + damping * (S[v] + dc / N), evaluated exactly
+ * as the scalar form (rounded add and multiply, no contraction).  t holds the teleport *term
+ * itself*, not a probability: a vector of all 0.15 gives ranks bitwise equal to the scalar run.
+ * While a vector is set, the scalar `teleport` of pr_reset / pr_run / pr_group_reset is ignored;
+ * `damping` still applies.  Everything else stays Sparky's: ranks are never normalised, S = r_old
+ * for rows without in-links, and the dangling term stays the uniform dc / N -- redistributing the
+ * dangling mass according to t is out of scope.
+ * The vector is a property of the handle: it survives pr_reset and pr_run (which reset ranks
+ * only), takes effect from the next iteration enqueued after the call, and is cleared by passing
+ * NULL (back to the scalar).  Both calls wait for the enqueued steps, like pr_get_ranks, and are
+ * valid any time after create, before or after pr_reset.  On a part the call is local, not
+ * collective: the part keeps only the rows it owns, so callers of a group (pr_group_*) or of RCCL
+ * ranks call it on every part with the same arguments.
+ * The first set allocates 8 bytes per local row, counted in PR_INFO_DEVICE_BYTES from then until
+ * pr_graph_destroy (NULL keeps the allocation); a handle that never sets a vector allocates
+ * nothing and launches exactly the kernels of the scalar run.
+ * Errors: a NULL graph, n < 0, NULL ids / values with n > 0, an ID outside [0, V), a duplicate
+ * ID, or a non-finite value or `rest`: PR_ERR_INVALID (checked on the host before any device call);
+ * an allocation failure: PR_ERR_OOM.  Nothing changes in either case. */
+/* V doubles in original-ID order (this part keeps its own rows'), or NULL: back to the scalar. */
+int pr_set_teleport(pr_graph *g, const double *teleport);
+/* t[ids[i]] = values[i], every other vertex `rest`.  ids must be distinct and in [0, V). */
+int pr_set_teleport_sparse(pr_graph *g, int32_t n, const int32_t *ids, const double *values, double rest);
+
 /* Top-K query, selected on the device: the k highest-ranked vertices of this part (the rows it
  * owns; with one part, of the graph), rank descending, ties broken by original vertex ID
  * ascending.  Ranks compare by the order-preserving map of their IEEE-754 bits to a u64 (sign bit

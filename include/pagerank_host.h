@@ -54,6 +54,21 @@ int prh_write_has_rank_ids(const prh_edges *e, const char *path, const int32_t *
 int prh_read_ranks(const prh_edges *e, const char *dir, double *ranks);
 void prh_free(prh_edges *e);
 
+/* ---- seeds of a personalised run (--seeds FILE; pr_set_teleport_sparse) ------------------ */
+/* Seed file: one "url" or "url<ws>weight" per line (weight finite and > 0, default 1); blank lines and
+   lines starting with '#' skipped.  ids/weights: malloc'ed, n entries, file order; prh_free_seeds frees.
+   A URL that is not in the edge list, a URL listed twice, a bad weight, anything after the weight,
+   or an empty seed set (n is at least 1) fails with a message that names the line. */
+int prh_read_seeds(const prh_edges *e, const char *path, int32_t *n, int32_t **ids, double **weights);
+/* the same from a memory buffer: exactly len bytes are read (no terminator needed) */
+int prh_parse_seeds(const prh_edges *e, const char *data, int64_t len, int32_t *n, int32_t **ids, double **weights);
+void prh_free_seeds(int32_t *ids, double *weights);
+/* The seeds' teleport terms: the total teleport mass stays teleport * n_vertices (0.15 N, Sparky's
+   scale), shared in proportion to the weights; every other vertex gets 0.
+   values[i] = ((teleport * (double)n_vertices) * weights[i]) / W,  W = weights summed left to right
+   The order of the operations is part of the interface: every host computes the same bits. */
+void prh_seed_teleport(int32_t n, const double *weights, double teleport, int32_t n_vertices, double *values);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <new>
 #include <string>
@@ -50,6 +51,7 @@ size_t pr_graph::device_bytes() const {
   b += units.bytes + unit_part.bytes + lr_row.bytes + lr_p0.bytes + piece_part.bytes;
   b += fin_part.bytes + fin_counter.bytes + reset_part.bytes + x_send.bytes + x_sbuf.bytes + hpos.bytes + cside.bytes;
   b += pr::topk_bytes(this);  // 0 until the first pr_get_topk
+  b += tele.bytes;            // 0 until the first pr_set_teleport / pr_set_teleport_sparse
   return b;
 }
 
@@ -261,6 +263,35 @@ int pr_reset(pr_graph *g, double teleport, double damping, const double *init_ra
   g->teleport = teleport;
   g->damping = damping;
   return pr::iter_reset(g, init_ranks);
+}
+
+int pr_set_teleport(pr_graph *g, const double *teleport) {
+  if (!g) return fail(PR_ERR_INVALID, "NULL graph");
+  if (teleport)  // host checks first: nothing below touches the device before they pass
+    for (int32_t v = 0; v < g->V; ++v)
+      if (!std::isfinite(teleport[v])) return fail(PR_ERR_INVALID, "teleport[" + std::to_string(v) + "] is not finite");
+  DeviceGuard dg(g->device);
+  return teleport ? pr::set_teleport_dense(g, teleport) : pr::clear_teleport(g);
+}
+
+int pr_set_teleport_sparse(pr_graph *g, int32_t n, const int32_t *ids, const double *values, double rest) {
+  if (!g) return fail(PR_ERR_INVALID, "NULL graph");
+  if (n < 0) return fail(PR_ERR_INVALID, "n < 0");
+  if (n > 0 && (!ids || !values)) return fail(PR_ERR_INVALID, "NULL argument");
+  if (!std::isfinite(rest)) return fail(PR_ERR_INVALID, "rest is not finite");
+  for (int32_t i = 0; i < n; ++i) {
+    if (ids[i] < 0 || ids[i] >= g->V)
+      return fail(PR_ERR_INVALID, "ids[" + std::to_string(i) + "] = " + std::to_string(ids[i]) + " is outside [0, V)");
+    if (!std::isfinite(values[i])) return fail(PR_ERR_INVALID, "values[" + std::to_string(i) + "] is not finite");
+  }
+  if (n > 1) {  // distinct IDs: a sorted copy has no equal neighbours
+    std::vector<int32_t> sorted(ids, ids + n);
+    std::sort(sorted.begin(), sorted.end());
+    const auto dup = std::adjacent_find(sorted.begin(), sorted.end());
+    if (dup != sorted.end()) return fail(PR_ERR_INVALID, "vertex " + std::to_string(*dup) + " is listed twice in ids");
+  }
+  DeviceGuard dg(g->device);
+  return pr::set_teleport_sparse(g, n, ids, values, rest);
 }
 
 int pr_step(pr_graph *g, int32_t iterations) {

@@ -121,6 +121,11 @@ struct pr_graph {
 
   // run state
   double teleport = 0.15, damping = 0.85;
+  // personalised PageRank (pr_set_teleport): the per-row teleport terms, n_rows doubles in row order
+  // (holes hold 0 or `rest`; no kernel reads them).  Allocated by the first set and kept until
+  // destroy; while tele_on, the update kernels read tele[row] and ignore the scalar above.
+  pr::DevBuf tele;
+  bool tele_on = false;
   int cur = 0;  // cbuf[cur] holds the contributions of the current ranks
   int64_t iters_done = 0;
   bool ready = false;  // pr_reset was called
@@ -216,6 +221,13 @@ int iter_reset(pr_graph *g, const double *init_ranks_host);
 int plan_epi_walk(pr_graph *g);  // per-row walk of sparse epilogue groups (after rmask/cbase)
 int plan_epi_order(pr_graph *g);  // dispatch order of the epilogue groups (after cbase)
 int prepare_hot_kernel();  // lets k_spmv_hot use up to 160 KiB of dynamic LDS (current device)
+int prepare_tele_kernels(const pr_graph *g);  // the same for the epilogue that reads a teleport vector
+// Personalised PageRank (pr_iter.hip): wait for g's enqueued work, then upload the teleport vector --
+// dense (V doubles in original-ID order, this part keeps its rows'), sparse (n distinct IDs in range
+// with their values, every other vertex `rest`; the caller has validated them) -- or clear it.
+int set_teleport_dense(pr_graph *g, const double *teleport);
+int set_teleport_sparse(pr_graph *g, int32_t n, const int32_t *ids, const double *values, double rest);
+int clear_teleport(pr_graph *g);
 // the heavy-row pass (k_spmv_hot) on g's stream, hot phases [ph0, ph1) (-1: all)
 int launch_hot(pr_graph *g, int in_buf, int ph0 = 0, int ph1 = -1);
 int join_exchange(pr_graph *g);  // g's stream waits for a pending overlapped exchange

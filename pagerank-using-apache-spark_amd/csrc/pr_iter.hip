@@ -21,6 +21,10 @@
 //                    its gather slice (last-arriving workgroup, agent-scope protocol of
 //                    cdna_hip_programming.md Guideline 16).
 //   P > 1: the exchange (pr_exchange.hip) sends every peer the contributions its in-links read.
+//   Personalised PageRank (pr_set_teleport): while a handle holds a teleport vector, the three
+//   update sites (k_spmv_units, k_finalize's long rows, k_epilogue_grp) run as their TELE
+//   instantiations, which read the row's own term t[row] in place of the scalar 0.15; a handle
+//   without one launches the TELE = false instantiations, the kernels it always launched.
 //
 // Every sum has a fixed order, so results are bitwise reproducible run to run.
 #include <algorithm>
@@ -44,13 +48,14 @@ __device__ __forceinline__ double load_sc1(const double *p) {
       reinterpret_cast<const unsigned long long *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 }
 
+template <bool TELE>
 __global__ __launch_bounds__(kThreads) void k_finalize(
     int64_t n_long, const int32_t *__restrict__ lr_row, const int32_t *__restrict__ lr_p0,
     const double *__restrict__ piece_part, const double2 *__restrict__ parts, int64_t n_parts,
     double *__restrict__ r, const uint32_t *__restrict__ rowinfo, const double *__restrict__ cin,
     double *__restrict__ cout, SlotPos sp, double n_vertices, double teleport,
     double damping, double *__restrict__ fin_part, unsigned *__restrict__ counter,
-    double *__restrict__ slot_out, PackSlots ps) {
+    double *__restrict__ slot_out, PackSlots ps, const double *__restrict__ tele) {
   __shared__ double red[kThreads / kWave];
   __shared__ int is_last;
   const int t = threadIdx.x, lane = lane_id();
@@ -66,7 +71,9 @@ __global__ __launch_bounds__(kThreads) void k_finalize(
       if (lane == 0) {
         const int32_t v = lr_row[q];
         const double rold = r[v];
-        const double rn = affine(acc, tdc, teleport, damping);
+        double tv = teleport;
+        if constexpr (TELE) tv = tele[v];
+        const double rn = affine(acc, tdc, tv, damping);
         r[v] = rn;
         const uint32_t info = rowinfo[v];
         const uint32_t d = info & kRowDegMask;
@@ -143,12 +150,14 @@ int launch_finalize(pr_graph *g, int64_t n_long, const double2 *parts, int64_t n
     for (int q = 0; q < g->nparts; ++q)
       if (q != g->part) ps.off[ps.n++] = g->x_soff[q + 1] - 2;
   }
-  hipLaunchKernelGGL(k_finalize, dim3(g->fin_blocks), dim3(kThreads), 0, stream, n_long,
-                     g->lr_row.as<int32_t>(), g->lr_p0.as<int32_t>(), g->piece_part.as<double>(),
+  // the per-row teleport terms matter to the long rows only (the reset's call has none)
+  const bool tele = g->tele_on && n_long > 0;
+  hipLaunchKernelGGL((tele ? k_finalize<true> : k_finalize<false>), dim3(g->fin_blocks), dim3(kThreads), 0, stream,
+                     n_long, g->lr_row.as<int32_t>(), g->lr_p0.as<int32_t>(), g->piece_part.as<double>(),
                      parts, n_parts, g->r.as<double>(), g->rowinfo.as<uint32_t>(),
                      g->cbuf[in_buf].as<double>(), cout, g->slots, (double)g->V,
                      g->teleport, g->damping, g->fin_part.as<double>(), g->fin_counter.as<unsigned>(),
-                     cout + g->S_pad - 2, ps);
+                     cout + g->S_pad - 2, ps, tele ? g->tele.as<double>() : nullptr);
   PR_HIP(hipGetLastError());
   return PR_OK;
 }
@@ -181,6 +190,15 @@ int prepare_hot_kernel() {
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)epi_grp_lds(narrow)));
       }
   // k_spmv_hot holds its LDS statically (kHotLdsBytes): no dynamic-LDS attribute to raise
+  return PR_OK;
+}
+
+// The TELE instantiations of k_epilogue_grp get the same dynamic-LDS allowance, on the first
+// pr_set_teleport of a handle (current device): a handle that never sets a vector never asks.
+int prepare_tele_kernels(const pr_graph *g) {
+  if (g->C <= 1) return PR_OK;
+  PR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(epi_grp_kernel(g->C, g->epi_walk, g->epi_narrow, true)),
+                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)epi_grp_lds(g->epi_narrow)));
   return PR_OK;
 }
 
@@ -433,13 +451,16 @@ int iter_compute(pr_graph *g) {
   if (!phased_wait) PR_TRY(join_exchange(g));
   else PR_HIP(hipStreamWaitEvent(s, g->x_ev[0], 0));  // phase 0's chunk
   PR_TRY(mark_start());
+  // the handle's teleport vector (pr_set_teleport), or nullptr: the scalar
+  const double *tele = g->tele_on ? g->tele.as<double>() : nullptr;
   // light rows (all rows when C == 1): fused single pass
   if (g->n_units > 0)
-    hipLaunchKernelGGL((k_spmv_units<kPerThread, true>), dim3((unsigned)g->n_units), dim3(kThreads), 0, s,
+    hipLaunchKernelGGL((tele ? k_spmv_units<kPerThread, true, true> : k_spmv_units<kPerThread, true, false>),
+                       dim3((unsigned)g->n_units), dim3(kThreads), 0, s,
                        g->units.as<Unit>(), g->rowptr.as<int64_t>(), g->colp.as<int32_t>(),
                        g->cbuf[in].as<double>(), g->cbuf[out].as<double>() + own, g->r.as<double>(),
                        g->rowinfo.as<uint32_t>(), g->piece_part.as<double>(), g->unit_part.as<double2>(),
-                       g->slots, g->S_pad, (double)g->V, g->teleport, g->damping);
+                       g->slots, g->S_pad, (double)g->V, g->teleport, g->damping, tele);
   int64_t n_parts = g->n_units;
   if (g->C > 1) {  // split layout: class units, long segments, then the epilogue over all rows
     if (phased_wait) {
@@ -460,7 +481,7 @@ int iter_compute(pr_graph *g) {
       hipLaunchKernelGGL(k_seg_reduce, dim3(grid_for(g->n_segs, kThreads / kWave, 4096)), dim3(kThreads), 0, s,
                          g->n_segs, g->seg_slot.as<int64_t>(), g->seg_p0.as<int32_t>(), g->piece_part.as<double>(),
                          g->partial.as<double>());
-    const EpiGrpFn epi = epi_grp_kernel(g->C, g->epi_walk, g->epi_narrow);
+    const EpiGrpFn epi = epi_grp_kernel(g->C, g->epi_walk, g->epi_narrow, tele != nullptr);
     PackDst pd{};  // fused pack: c' straight into the send runs paired with buffer `out`
     if (g->x_fused) {
       pd.sbuf = send_runs(g, out);
@@ -477,7 +498,7 @@ int iter_compute(pr_graph *g) {
                          g->rowinfo.as<uint32_t>(), g->r.as<double>(), g->cbuf[out].as<double>() + own,
                          g->cbuf[in].as<double>(), g->slots, (double)g->V, g->teleport, g->damping,
                          g->unit_part.as<double2>() + g->n_units, g->eoff.as<int64_t>(), g->epos.as<uint16_t>(),
-                         g->x_pmask.as<uint8_t>(), g->x_sbase.as<int32_t>(), ord, pd);
+                         g->x_pmask.as<uint8_t>(), g->x_sbase.as<int32_t>(), ord, pd, tele);
       PR_HIP(hipGetLastError());
       return PR_OK;
     };
@@ -587,6 +608,104 @@ int read_slots(pr_graph *g, int buf, double *dc, double *l1) {
   }
   *dc = a;
   *l1 = b;
+  return PR_OK;
+}
+
+// ---- personalised PageRank: the handle's teleport vector (pr_set_teleport*) -------------------
+namespace {
+// every row's term = value (the sparse form's `rest`)
+__global__ __launch_bounds__(kThreads) void k_tele_fill(int64_t rows, double value, double *__restrict__ tele) {
+  for (int64_t j = (int64_t)blockIdx.x * kThreads + threadIdx.x; j < rows; j += (int64_t)gridDim.x * kThreads)
+    tele[j] = value;
+}
+// the sparse form's seeds: tele[rows[i]] = values[i] (distinct rows, all < the vector's length)
+__global__ __launch_bounds__(kThreads) void k_tele_scatter(int64_t n, const int64_t *__restrict__ rows,
+                                                           const double *__restrict__ values,
+                                                           double *__restrict__ tele) {
+  for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kThreads)
+    tele[rows[i]] = values[i];
+}
+
+// the enqueued steps are done with the old terms before the vector changes
+int tele_quiesce(pr_graph *g) {
+  PR_TRY(join_exchange(g));
+  PR_HIP(hipStreamSynchronize(g->stream));
+  return PR_OK;
+}
+
+// g->tele exists (n_rows doubles; allocated once, kept until destroy)
+int tele_ensure(pr_graph *g) {
+  if (g->tele.p) return PR_OK;
+  DevBuf b;
+  PR_TRY(b.alloc(sizeof(double) * ((size_t)g->n_rows + 1)));  // sized like g->r
+  PR_TRY(prepare_tele_kernels(g));
+  g->tele = std::move(b);
+  return PR_OK;
+}
+}  // namespace
+
+int clear_teleport(pr_graph *g) {
+  PR_TRY(tele_quiesce(g));
+  g->tele_on = false;  // the allocation stays (and stays counted) for the next set
+  return PR_OK;
+}
+
+int set_teleport_dense(pr_graph *g, const double *teleport) {
+  PR_TRY(tele_quiesce(g));
+  std::vector<double> loc((size_t)g->n_rows, 0.0);  // this part's rows, as iter_reset places init ranks
+  for (int64_t L = 0; L < g->n_rows; ++L)
+    if (g->orig_of_local[L] >= 0) loc[L] = teleport[g->orig_of_local[L]];
+  PR_TRY(tele_ensure(g));
+  if (g->n_rows > 0) {
+    PR_HIP(hipMemcpyAsync(g->tele.p, loc.data(), sizeof(double) * g->n_rows, hipMemcpyHostToDevice, g->stream));
+    PR_HIP(hipStreamSynchronize(g->stream));
+  }
+  g->tele_on = true;
+  return PR_OK;
+}
+
+// The original-ID -> row map is never materialised: a kept one would be V ints for one part, as
+// much again as orig_of_local itself.  The n seeds are sorted by ID once per call (the caller's
+// duplicate check sorted them the same way) and one pass over orig_of_local looks every row's ID
+// up in them: O(rows log n) time, O(n) memory.
+int set_teleport_sparse(pr_graph *g, int32_t n, const int32_t *ids, const double *values, double rest) {
+  PR_TRY(tele_quiesce(g));
+  std::vector<std::pair<int32_t, int32_t>> seeds((size_t)n);  // (ID, index)
+  for (int32_t i = 0; i < n; ++i) seeds[i] = {ids[i], i};
+  std::sort(seeds.begin(), seeds.end());
+  std::vector<int64_t> rows;
+  std::vector<double> vals;
+  if (n > 0)
+    for (int64_t L = 0; L < g->n_rows; ++L) {
+      const int32_t id = g->orig_of_local[L];
+      if (id < 0) continue;
+      const auto it = std::lower_bound(seeds.begin(), seeds.end(), std::make_pair(id, (int32_t)0));
+      if (it == seeds.end() || it->first != id) continue;
+      rows.push_back(L);
+      vals.push_back(values[it->second]);
+    }
+  const int64_t m = (int64_t)rows.size();  // the seeds this part owns
+  DevBuf drows, dvals;
+  if (m > 0) {
+    PR_TRY(drows.alloc(sizeof(int64_t) * (size_t)m));
+    PR_TRY(dvals.alloc(sizeof(double) * (size_t)m));
+  }
+  PR_TRY(tele_ensure(g));
+  hipStream_t s = g->stream;
+  if (g->n_rows > 0) {
+    hipLaunchKernelGGL(k_tele_fill, dim3(grid_for(g->n_rows, kThreads, 4096)), dim3(kThreads), 0, s, g->n_rows, rest,
+                       g->tele.as<double>());
+    PR_HIP(hipGetLastError());
+  }
+  if (m > 0) {
+    PR_HIP(hipMemcpyAsync(drows.p, rows.data(), sizeof(int64_t) * (size_t)m, hipMemcpyHostToDevice, s));
+    PR_HIP(hipMemcpyAsync(dvals.p, vals.data(), sizeof(double) * (size_t)m, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_tele_scatter, dim3(grid_for(m, kThreads, 4096)), dim3(kThreads), 0, s, m, drows.as<int64_t>(),
+                       dvals.as<double>(), g->tele.as<double>());
+    PR_HIP(hipGetLastError());
+  }
+  PR_HIP(hipStreamSynchronize(s));  // the staging buffers go out of scope
+  g->tele_on = true;
   return PR_OK;
 }
 

@@ -27,6 +27,10 @@ __device__ __forceinline__ double dc_from_slots(const double *cin, const SlotPos
 }
 
 // r' = teleport + damping * (S + tdc), evaluated exactly as Sparky.java:233 (no contraction).
+// Personalised PageRank (pr_set_teleport): kernels instantiated with TELE = true read the row's own
+// teleport term from `tele` (row order, one double per local row, holes included) in the scalar's
+// place; the expression and its rounding are the same.  The TELE = false instantiations are the
+// kernels of a handle without a vector: they never touch `tele`.
 __device__ __forceinline__ double affine(double S, double tdc, double teleport, double damping) {
   return __dadd_rn(teleport, __dmul_rn(damping, __dadd_rn(S, tdc)));
 }
@@ -69,13 +73,13 @@ __device__ __forceinline__ void load_cols(const int32_t *__restrict__ p, int32_t
 //     rows (coalesced) and fuses the in-degree-0 quirk, r' = 0.15 + 0.85 (S + dc/N) without FMA,
 //     c' = r'/d, the partial sum of r' over sink rows and the partial L1 norm.
 //   PIECE unit (PT*256 in-links of one long row): one fixed-order block sum -> piece_part.
-template <int PT, bool NT>
+template <int PT, bool NT, bool TELE>
 __global__ __launch_bounds__(kThreads) void k_spmv_units(
     const Unit *__restrict__ units, const int64_t *__restrict__ rowptr,
     const int32_t *__restrict__ colp, const double *__restrict__ cin, double *__restrict__ cout,
     double *__restrict__ r, const uint32_t *__restrict__ rowinfo, double *__restrict__ piece_part,
     double2 *__restrict__ unit_part, SlotPos sp, int64_t S_pad, double n_vertices, double teleport,
-    double damping) {
+    double damping, const double *__restrict__ tele) {
   __shared__ double rowsum[kUnitRows];
   __shared__ int32_t lrp[kUnitRows + 1];
   __shared__ double red[kThreads / kWave];
@@ -102,13 +106,14 @@ __global__ __launch_bounds__(kThreads) void k_spmv_units(
     for (int j = 0; j < PT; ++j) ci[j] = 0;
   }
   int64_t rp_t = 0;
-  double rold0 = 0.0;
+  double rold0 = 0.0, tele0 = teleport;
   uint32_t info0 = 0;
   if (stream) {
     if (t <= nr) rp_t = rowptr[r0 + t];
     if (t < nr) {
       rold0 = r[(int64_t)r0 + t];
       info0 = rowinfo[(int64_t)r0 + t];
+      if constexpr (TELE) tele0 = tele[(int64_t)r0 + t];
     }
   }
 
@@ -225,7 +230,9 @@ __global__ __launch_bounds__(kThreads) void k_spmv_units(
     const uint32_t info = (k == t) ? info0 : rowinfo[vtx];
     if (info & kRowHole) continue;
     const double S = (lrp[k + 1] > lrp[k]) ? rowsum[k] : rold;
-    const double rn = affine(S, tdc, teleport, damping);
+    double tv = teleport;
+    if constexpr (TELE) tv = (k == t) ? tele0 : tele[vtx];
+    const double rn = affine(S, tdc, tv, damping);
     r[vtx] = rn;
     const uint32_t d = info & kRowDegMask;
     if (d > 0) cout[vtx] = __ddiv_rn(rn, (double)d);
@@ -1001,6 +1008,7 @@ struct EpiArgs {
   const uint16_t *epos;
   const uint8_t *pmask;
   const int32_t *sbase;
+  const double *tele;  // per-row teleport terms (TELE instantiations only)
 };
 
 // Cache policy of the epilogue's LDS-DMA of the partial runs (aux bits); A/B builds only.
@@ -1010,6 +1018,13 @@ struct EpiArgs {
 #ifndef PR_EPI_LATE_ROW
 #define PR_EPI_LATE_ROW 0  // 1: k_epilogue_grp loads rowinfo / r after the class loop (A/B builds)
 #endif
+// Where the TELE instantiations of k_epilogue_grp load a group's eight teleport terms: 0 (product)
+// after the class loop, each in its block's update, so none is live through the loop -- the
+// instantiations then need the VGPRs of their scalar twins; 1 next to rold (A/B builds): 14 more
+// VGPRs, and the 64-class walk and the 128-class kernels spill to scratch (profiles/ppr/README.md).
+#ifndef PR_EPI_TELE_EARLY
+#define PR_EPI_TELE_EARLY 0
+#endif
 
 // One group gi (kEpiGroup consecutive 64-row blocks) of the grouped epilogue, by one wave with its
 // LDS window win (kEpiWin slots + the zero slot win[kEpiWin]).  The group's dangling and L1
@@ -1017,7 +1032,7 @@ struct EpiArgs {
 // same order whichever wave, workgroup or launch ran the group: every epilogue schedule and grid
 // shape is bitwise the same (round 4's overlapped-epilogue schedules relied on it; they were
 // measured slower and removed, profiles/r04/README.md).  The body of k_epilogue_grp (below).
-template <int C, bool WALK>
+template <int C, bool WALK, bool TELE>
 __device__ __forceinline__ void epi_group(const EpiArgs &a, const PackDst &pd, int64_t gi, double tdc, double *win,
                                           double2 *__restrict__ ep_part) {
   double dcp = 0.0, l1p = 0.0;
@@ -1031,6 +1046,7 @@ __device__ __forceinline__ void epi_group(const EpiArgs &a, const PackDst &pd, i
   const int nb = (int)min((int64_t)G, a.nblk - b0);
   uint32_t mw[MW][G], info[G];
   double rold[G], S[G];
+  double tv[G];     // the rows' teleport terms (TELE)
   double cnv[G];    // c' per block, for the fused pack
   uint32_t pmv[G];  // the peers that read the row, per block
 #pragma unroll
@@ -1051,6 +1067,9 @@ __device__ __forceinline__ void epi_group(const EpiArgs &a, const PackDst &pd, i
 #if !PR_EPI_LATE_ROW
     info[g] = ok ? a.rowinfo[L] : kRowHole;
     rold[g] = ok ? a.r[L] : 0.0;
+#endif
+#if PR_EPI_TELE_EARLY
+    if constexpr (TELE) tv[g] = ok ? a.tele[L] : 0.0;
 #endif
     S[g] = 0.0;
   }
@@ -1181,12 +1200,16 @@ __device__ __forceinline__ void epi_group(const EpiArgs &a, const PackDst &pd, i
 #pragma unroll
   for (int g = 0; g < G; ++g) {
     const int64_t L = (b0 + g) * kWave + lane;
+    if constexpr (!TELE) tv[g] = a.teleport;
+#if !PR_EPI_TELE_EARLY
+    else tv[g] = g < nb ? a.tele[L] : 0.0;
+#endif
     double Sv = S[g];
     uint32_t any = 0u;
 #pragma unroll
     for (int w = 0; w < MW; ++w) any |= mw[w][g];
     if (any == 0u) Sv = rold[g];  // no in-link: subtractByKey + union keeps the old rank (Sparky.java:224-225)
-    const double rn = affine(Sv, tdc, a.teleport, a.damping);
+    const double rn = affine(Sv, tdc, tv[g], a.damping);
     double cn = 0.0;
     if (!(info[g] & kRowHole)) {
       a.r[L] = rn;
@@ -1244,18 +1267,18 @@ __device__ __forceinline__ void epi_group(const EpiArgs &a, const PackDst &pd, i
 #else
 #define PR_EPI_BOUNDS(NT) __launch_bounds__(NT, 4)
 #endif
-template <int C, bool WALK, int NT>
+template <int C, bool WALK, int NT, bool TELE>
 __global__ PR_EPI_BOUNDS(NT) void k_epilogue_grp(
     int64_t nblk, int64_t g_lo, int64_t g_hi, const double *__restrict__ partial, const void *__restrict__ rmask_v,
     const int32_t *__restrict__ cbase, const uint32_t *__restrict__ rowinfo, double *__restrict__ r,
     double *__restrict__ cout, const double *__restrict__ cin, SlotPos sp, double n_vertices, double teleport,
     double damping, double2 *__restrict__ ep_part /* [group] */, const int64_t *__restrict__ eoff,
     const uint16_t *__restrict__ epos, const uint8_t *__restrict__ pmask, const int32_t *__restrict__ sbase,
-    const int32_t *__restrict__ order, PackDst pd) {
+    const int32_t *__restrict__ order, PackDst pd, const double *__restrict__ tele) {
   constexpr int W = kEpiWin;
   constexpr int NW = NT / kWave;
   extern __shared__ double epi_lds[];  // NW windows of W + 2 slots
-  const EpiArgs a{nblk, partial, rmask_v, cbase, rowinfo, r, cout, teleport, damping, eoff, epos, pmask, sbase};
+  const EpiArgs a{nblk, partial, rmask_v, cbase, rowinfo, r, cout, teleport, damping, eoff, epos, pmask, sbase, tele};
   const int lane = lane_id();
   const int wv = __builtin_amdgcn_readfirstlane(wave_id());
   double *win = epi_lds + wv * (W + 2);
@@ -1265,7 +1288,7 @@ __global__ PR_EPI_BOUNDS(NT) void k_epilogue_grp(
   // order: the group of each dispatch position (heaviest first, plan_epi_order); the group's
   // partials go to its own ep_part slot, so the order changes no sum
   for (int64_t k = g_lo + (int64_t)blockIdx.x * NW + wv; k < g_hi; k += nw)
-    epi_group<C, WALK>(a, pd, order ? (int64_t)order[k] : k, tdc, win, ep_part);
+    epi_group<C, WALK, TELE>(a, pd, order ? (int64_t)order[k] : k, tdc, win, ep_part);
 }
 
 // Build-time plan of the per-row walk (WALK above), one wave per group of G 64-row blocks.
@@ -1345,23 +1368,29 @@ __global__ __launch_bounds__(kEpiThreads) void k_epi_walk_plan(int64_t nblk, con
 // four-wave workgroups
 using EpiGrpFn = void (*)(int64_t, int64_t, int64_t, const double *, const void *, const int32_t *, const uint32_t *, double *,
                           double *, const double *, SlotPos, double, double, double, double2 *, const int64_t *,
-                          const uint16_t *, const uint8_t *, const int32_t *, const int32_t *, PackDst);
-template <int C>
+                          const uint16_t *, const uint8_t *, const int32_t *, const int32_t *, PackDst, const double *);
+template <int C, bool TELE>
 inline EpiGrpFn epi_grp_kernel_c(bool walk, bool narrow) {
   if constexpr (C <= kWave) {
-    if (narrow) return walk ? k_epilogue_grp<C, true, kEpiThreadsNarrow> : k_epilogue_grp<C, false, kEpiThreadsNarrow>;
-    if (walk) return k_epilogue_grp<C, true, kEpiThreads>;
+    if (narrow)
+      return walk ? k_epilogue_grp<C, true, kEpiThreadsNarrow, TELE> : k_epilogue_grp<C, false, kEpiThreadsNarrow, TELE>;
+    if (walk) return k_epilogue_grp<C, true, kEpiThreads, TELE>;
   }
-  return k_epilogue_grp<C, false, kEpiThreads>;
+  return k_epilogue_grp<C, false, kEpiThreads, TELE>;
 }
-inline EpiGrpFn epi_grp_kernel(int C, bool walk, bool narrow) {
+template <bool TELE>
+inline EpiGrpFn epi_grp_kernel_t(int C, bool walk, bool narrow) {
   switch (C) {
-    case 8: return epi_grp_kernel_c<8>(walk, narrow);
-    case 16: return epi_grp_kernel_c<16>(walk, narrow);
-    case 32: return epi_grp_kernel_c<32>(walk, narrow);
-    case 64: return epi_grp_kernel_c<64>(walk, narrow);
-    default: return epi_grp_kernel_c<128>(false, false);
+    case 8: return epi_grp_kernel_c<8, TELE>(walk, narrow);
+    case 16: return epi_grp_kernel_c<16, TELE>(walk, narrow);
+    case 32: return epi_grp_kernel_c<32, TELE>(walk, narrow);
+    case 64: return epi_grp_kernel_c<64, TELE>(walk, narrow);
+    default: return epi_grp_kernel_c<128, TELE>(false, false);
   }
+}
+// tele: the instantiations that read per-row teleport terms (a handle with pr_set_teleport in force)
+inline EpiGrpFn epi_grp_kernel(int C, bool walk, bool narrow, bool tele = false) {
+  return tele ? epi_grp_kernel_t<true>(C, walk, narrow) : epi_grp_kernel_t<false>(C, walk, narrow);
 }
 
 }  // namespace pr

@@ -2,7 +2,7 @@
 //
 //   pagerank <input-path> [iterations=10] [--format=edges|ccjson] [--out DIR]
 //            [--save-every-iter] [--dangling=local|none] [--device N] [--quiet] [--stats]
-//            [--resume DIR/PageRank<i>] [--devices D0,D1,...] [--top K]
+//            [--resume DIR/PageRank<i>] [--devices D0,D1,...] [--top K] [--seeds FILE]
 //
 // Input (libpagerank_host): "src dst" edge list ("src" alone = record without links), or
 // --format=ccjson "url<TAB>json" Common Crawl metadata records (Sparky.java:61-123).  URLs are
@@ -21,6 +21,13 @@
 // --top K: the final listing is only the K highest-ranked URLs, rank descending, ties by first
 // appearance in the input (= ID ascending), selected on the GPU (pr_get_topk / pr_group_topk).
 // Without --out the rank vector never crosses to the host; --out still writes complete part files.
+// --seeds FILE: personalised PageRank.  FILE lists the seed URLs, one "url" or "url weight" per line
+// (weight > 0, default 1; blank lines and '#' lines skipped): the teleport mass 0.15 N goes to the
+// seeds in proportion to their weights and every other URL's teleport term is 0
+// (prh_seed_teleport, pr_set_teleport_sparse); the dangling term stays uniform.  The file is read
+// and checked before the graph is created: a bad one exits with status 2 without touching a GPU.
+// Combines with every other option; outputs have the same form as without it.
+//   pagerank edges.txt 20 --seeds seeds.txt --top 100
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -33,7 +40,7 @@
 namespace {
 
 struct Options {
-  std::string path, out, resume;
+  std::string path, out, resume, seeds;
   int iterations = 10;  // Sparky.java:187
   int format = PRH_FORMAT_EDGES;
   bool save_every = false, quiet = false, stats = false;
@@ -62,7 +69,7 @@ std::vector<int> parse_devices(const std::string &s) {
   std::fprintf(stderr,
                "usage: pagerank <input-path> [iterations=10] [--format=edges|ccjson] [--out DIR]\n"
                "                [--save-every-iter] [--dangling=local|none] [--device N] [--quiet] [--stats]\n"
-               "                [--resume DIR/PageRank<i>] [--devices D0,D1,...] [--top K]\n");
+               "                [--resume DIR/PageRank<i>] [--devices D0,D1,...] [--top K] [--seeds FILE]\n");
   std::exit(2);
 }
 
@@ -83,6 +90,8 @@ Options parse(int argc, char **argv) {
     else if (a == "--device" && i + 1 < argc) o.device = std::atoi(argv[++i]);
     else if (a == "--resume" && i + 1 < argc) o.resume = argv[++i];
     else if (a.rfind("--resume=", 0) == 0) o.resume = a.substr(9);
+    else if (a == "--seeds" && i + 1 < argc) o.seeds = argv[++i];
+    else if (a.rfind("--seeds=", 0) == 0) o.seeds = a.substr(8);
     else if ((a == "--devices" && i + 1 < argc) || a.rfind("--devices=", 0) == 0) {
       o.devices = parse_devices(a == "--devices" ? std::string(argv[++i]) : a.substr(10));
       if (o.devices.empty()) usage("--devices takes a comma-separated list of device numbers");
@@ -103,6 +112,13 @@ Options parse(int argc, char **argv) {
   if (o.iterations < 0) usage("iterations must be >= 0");
   return o;
 }
+
+// --seeds: the seed IDs and their teleport terms (prh_seed_teleport); n == 0: a uniform run
+struct Seeds {
+  int32_t n = 0;
+  int32_t *ids = nullptr;
+  std::vector<double> values;
+};
 
 struct Job {
   const Options *opt;
@@ -140,7 +156,7 @@ void on_iter(int32_t it_run, const double *ranks, double dc, double l1, double m
 // --devices: build one part per device, then run the iterations as a single-process group with
 // the same callback protocol as pr_run (ranks merged from every part, dc / L1 from part 0's
 // stats, which sum every part's slots).
-int run_group(const Options &o, const prh_edges *edges, const double *init, int n_run, Job *job,
+int run_group(const Options &o, const prh_edges *edges, const Seeds &seeds, const double *init, int n_run, Job *job,
               std::vector<double> *ranks, std::vector<int32_t> *top_ids, std::vector<double> *top_ranks) {
   const int P = (int)o.devices.size();
   const int32_t V = prh_n_vertices(edges);
@@ -150,6 +166,8 @@ int run_group(const Options &o, const prh_edges *edges, const double *init, int 
     rc = pr_graph_create_part(o.devices[p], p, P, V, prh_n_edges(edges), prh_src(edges), prh_dst(edges),
                               o.flags | PR_NO_CANONICAL, &parts[p]);
   const bool want = !o.out.empty();
+  for (int p = 0; p < P && rc == PR_OK && seeds.n > 0; ++p)  // every part, the same arguments
+    rc = pr_set_teleport_sparse(parts[p], seeds.n, seeds.ids, seeds.values.data(), 0.0);
   if (rc == PR_OK) rc = pr_group_reset(parts.data(), P, 0.15, 0.85, init);
   for (int it = 0; it < n_run && rc == PR_OK; ++it) {
     const auto t0 = std::chrono::steady_clock::now();
@@ -191,6 +209,18 @@ int main(int argc, char **argv) {
     return 1;
   }
   const int32_t V = prh_n_vertices(edges);
+  Seeds seeds;
+  if (!o.seeds.empty()) {  // read and checked before any graph exists: a bad file costs no GPU work
+    double *weights = nullptr;
+    if (prh_read_seeds(edges, o.seeds.c_str(), &seeds.n, &seeds.ids, &weights) != 0) {
+      std::fprintf(stderr, "pagerank: --seeds: %s\n", prh_last_error());
+      prh_free(edges);
+      return 2;
+    }
+    seeds.values.resize((size_t)seeds.n);
+    prh_seed_teleport(seeds.n, weights, 0.15, V, seeds.values.data());
+    prh_free_seeds(nullptr, weights);
+  }
   const double ms_read = ms_since(t_job);  // parse + first-appearance interning (host)
   double ms_build = 0.0, ms_run = 0.0;
   Job job{&o, edges};
@@ -212,7 +242,7 @@ int main(int argc, char **argv) {
   if (o.devices.size() > 1) {
     if (n_run > 0) std::printf("Starting iter%d\n", job.start);
     const auto t0 = Clock::now();
-    if (run_group(o, edges, init_p, n_run, &job, &ranks, &top_ids, &top_ranks) != PR_OK) {
+    if (run_group(o, edges, seeds, init_p, n_run, &job, &ranks, &top_ids, &top_ranks) != PR_OK) {
       prh_free(edges);
       return 1;
     }
@@ -225,6 +255,13 @@ int main(int argc, char **argv) {
     ms_build = ms_since(t0);
     if (rc != PR_OK) {
       std::fprintf(stderr, "pagerank: graph build failed (%d): %s\n", rc, pr_last_error());
+      prh_free(edges);
+      return 1;
+    }
+    if (seeds.n > 0 && (rc = pr_set_teleport_sparse(g, seeds.n, seeds.ids, seeds.values.data(), 0.0)) != PR_OK) {
+      std::fprintf(stderr, "pagerank: --seeds: (%d) %s\n", rc, pr_last_error());
+      pr_graph_destroy(g);
+      prh_free_seeds(seeds.ids, nullptr);
       prh_free(edges);
       return 1;
     }
@@ -270,6 +307,7 @@ int main(int argc, char **argv) {
                  "{\"job\": {\"urls\": %d, \"edge_records\": %lld, \"read_intern_ms\": %.1f, \"build_ms\": %.1f, "
                  "\"iterations\": %d, \"run_ms\": %.1f, \"has_rank_out_ms\": %.1f, \"total_ms\": %.1f}}\n",
                  V, (long long)prh_n_edges(edges), ms_read, ms_build, n_run, ms_run, ms_out, ms_since(t_job));
+  prh_free_seeds(seeds.ids, nullptr);
   prh_free(edges);
   return job.error;
 }

@@ -973,3 +973,108 @@ int prh_read_ranks(const prh_edges *e, const char *dir, double *ranks) {
 void prh_free(prh_edges *e) { delete e; }
 
 }  // extern "C"
+
+// ---- seeds of a personalised run (--seeds) ------------------------------------------------------
+namespace {
+
+// The seed lines of data[0, len): every read stays inside the buffer (a cut-off last line is
+// parsed as it stands).  Errors name `label` and the line.
+int parse_seed_lines(const prh_edges *e, const char *data, size_t len, const std::string &label, int32_t *n_out,
+                     int32_t **ids_out, double **weights_out) {
+  std::unordered_map<std::string_view, int32_t> id;
+  id.reserve(e->names.size() * 2);
+  for (size_t v = 0; v < e->names.size(); ++v) id.emplace(e->names[v], (int32_t)v);
+  std::unordered_map<int32_t, size_t> first_line;  // seed ID -> the line that listed it
+  std::vector<int32_t> ids;
+  std::vector<double> weights;
+  size_t i = 0, lineno = 0;
+  auto where = [&]() { return label + ": line " + std::to_string(lineno) + ": "; };
+  while (i < len) {
+    ++lineno;
+    const size_t b = i;
+    while (i < len && data[i] != '\n') ++i;
+    size_t t = i++;
+    if (t > b && data[t - 1] == '\r') --t;
+    std::string_view tok[2];
+    const int nt = edge_tokens(data, b, t, tok);
+    if (nt == 0 || tok[0][0] == '#') continue;  // blank line, comment
+    if (nt > 2) return fail(where() + "expected 'url' or 'url weight', got " + std::to_string(nt) + " tokens");
+    double w = 1.0;
+    if (nt == 2) {
+      const std::string num(tok[1]);
+      char *endp = nullptr;
+      w = std::strtod(num.c_str(), &endp);
+      if (endp == num.c_str() || *endp != '\0' || !std::isfinite(w) || !(w > 0.0))
+        return fail(where() + "bad weight '" + num + "' (a finite number > 0)");
+    }
+    const auto it = id.find(tok[0]);
+    if (it == id.end()) return fail(where() + "URL '" + std::string(tok[0]) + "' is not in the edge list");
+    const auto ins = first_line.emplace(it->second, lineno);
+    if (!ins.second)
+      return fail(where() + "URL '" + std::string(tok[0]) + "' is listed twice (first on line " +
+                  std::to_string(ins.first->second) + ")");
+    ids.push_back(it->second);
+    weights.push_back(w);
+  }
+  if (ids.empty()) {
+    ++lineno;  // where a first seed would have stood
+    return fail(where() + "no seed (the seed set is empty)");
+  }
+  int32_t *pi = static_cast<int32_t *>(std::malloc(sizeof(int32_t) * ids.size()));
+  double *pw = static_cast<double *>(std::malloc(sizeof(double) * weights.size()));
+  if (!pi || !pw) {
+    std::free(pi);
+    std::free(pw);
+    return fail(label + ": out of memory");
+  }
+  std::memcpy(pi, ids.data(), sizeof(int32_t) * ids.size());
+  std::memcpy(pw, weights.data(), sizeof(double) * weights.size());
+  *n_out = (int32_t)ids.size();
+  *ids_out = pi;
+  *weights_out = pw;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int prh_parse_seeds(const prh_edges *e, const char *data, int64_t len, int32_t *n, int32_t **ids, double **weights) {
+  if (!e || (!data && len > 0) || len < 0 || !n || !ids || !weights) return fail("bad argument");
+  *n = 0;
+  *ids = nullptr;
+  *weights = nullptr;
+  return parse_seed_lines(e, data, (size_t)len, "seeds", n, ids, weights);
+}
+
+int prh_read_seeds(const prh_edges *e, const char *path, int32_t *n, int32_t **ids, double **weights) {
+  if (!e || !path || !n || !ids || !weights) return fail("NULL argument");
+  *n = 0;
+  *ids = nullptr;
+  *weights = nullptr;
+  FILE *f = std::fopen(path, "rb");
+  if (!f) return fail(std::string("cannot open ") + path + ": " + std::strerror(errno));
+  std::string data;
+  char buf[1 << 16];
+  size_t k;
+  while ((k = std::fread(buf, 1, sizeof(buf), f)) > 0) data.append(buf, k);
+  std::fclose(f);
+  return parse_seed_lines(e, data.data(), data.size(), path, n, ids, weights);
+}
+
+void prh_free_seeds(int32_t *ids, double *weights) {
+  std::free(ids);
+  std::free(weights);
+}
+
+// The order of the operations is part of the interface (include/pagerank_host.h): every host
+// computes the same bits.  Built without contraction by construction: no a * b + c here.
+void prh_seed_teleport(int32_t n, const double *weights, double teleport, int32_t n_vertices, double *values) {
+  if (n <= 0 || !weights || !values) return;
+  double W = 0.0;
+  for (int32_t i = 0; i < n; ++i) W += weights[i];
+  const double mass = teleport * (double)n_vertices;
+  for (int32_t i = 0; i < n; ++i) values[i] = (mass * weights[i]) / W;
+}
+
+}  // extern "C"

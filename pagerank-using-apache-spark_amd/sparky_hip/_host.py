@@ -50,6 +50,12 @@ def load() -> ctypes.CDLL:
         L.prh_read_ranks.argtypes = [P, ctypes.c_char_p, P]
         L.prh_free.argtypes = [P]
         L.prh_free.restype = None
+        L.prh_read_seeds.argtypes = [P, ctypes.c_char_p, P, P, P]
+        L.prh_parse_seeds.argtypes = [P, ctypes.c_char_p, ctypes.c_int64, P, P, P]
+        L.prh_free_seeds.argtypes = [P, P]
+        L.prh_free_seeds.restype = None
+        L.prh_seed_teleport.argtypes = [ctypes.c_int32, P, ctypes.c_double, ctypes.c_int32, P]
+        L.prh_seed_teleport.restype = None
         L.prh_set_read_threads.argtypes = [ctypes.c_int32]
         L.prh_set_read_threads.restype = None
         _hl = L
@@ -126,6 +132,29 @@ class HostEdges:
         _check(load().prh_read_ranks(self._h, directory.encode(), r.ctypes.data_as(ctypes.c_void_p)))
         return r[: self.n_vertices]
 
+    def _seeds(self, rc, n, pi, pw):
+        _check(rc)
+        try:
+            ids = np.ctypeslib.as_array(ctypes.cast(pi, ctypes.POINTER(ctypes.c_int32)), shape=(n.value,)).copy()
+            w = np.ctypeslib.as_array(ctypes.cast(pw, ctypes.POINTER(ctypes.c_double)), shape=(n.value,)).copy()
+        finally:
+            load().prh_free_seeds(pi, pw)
+        return ids, w
+
+    def read_seeds(self, path: str):
+        """prh_read_seeds: the seed file's (ids int32[n], weights float64[n]) in file order (n >= 1);
+        a URL that is not in the edge list, a duplicate, a bad weight or an empty file raises
+        HostError with the line."""
+        n, pi, pw = ctypes.c_int32(0), ctypes.c_void_p(), ctypes.c_void_p()
+        rc = load().prh_read_seeds(self._h, path.encode(), ctypes.byref(n), ctypes.byref(pi), ctypes.byref(pw))
+        return self._seeds(rc, n, pi, pw)
+
+    def parse_seeds(self, data: bytes):
+        """prh_parse_seeds: read_seeds from a buffer."""
+        n, pi, pw = ctypes.c_int32(0), ctypes.c_void_p(), ctypes.c_void_p()
+        rc = load().prh_parse_seeds(self._h, data, len(data), ctypes.byref(n), ctypes.byref(pi), ctypes.byref(pw))
+        return self._seeds(rc, n, pi, pw)
+
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             load().prh_free(self._h)
@@ -137,6 +166,18 @@ class HostEdges:
             self.close()
         except Exception:
             pass
+
+
+def seed_teleport(weights, n_vertices: int, teleport: float = 0.15) -> np.ndarray:
+    """prh_seed_teleport: the seeds' teleport terms, ((teleport * N) * w[i]) / sum(w) in the native
+    library's operation order (both CLIs pass the same bits to pr_set_teleport_sparse)."""
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    if w.ndim != 1:
+        raise ValueError("weights must be a 1-D array")
+    out = np.zeros(max(w.shape[0], 1), np.float64)
+    load().prh_seed_teleport(int(w.shape[0]), w.ctypes.data_as(ctypes.c_void_p), float(teleport), int(n_vertices),
+                             out.ctypes.data_as(ctypes.c_void_p))
+    return out[: w.shape[0]]
 
 
 def java_double_native(x: float) -> str:

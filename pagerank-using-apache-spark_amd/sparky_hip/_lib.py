@@ -59,6 +59,7 @@ EXPORTED = [
     "pr_get_ranks", "pr_set_timing", "pr_set_option", "pr_get_stats", "pr_comm_unique_id", "pr_graph_attach_comm",
     "pr_graph_destroy", "pr_gen_rmat", "pr_gen_er", "pr_gen_chunglu", "pr_intern_device", "pr_group_reset",
     "pr_group_step", "pr_group_sync", "pr_get_topk", "pr_group_topk", "pr_topk_merge",
+    "pr_set_teleport", "pr_set_teleport_sparse",
 ]
 
 ITER_CB = ctypes.CFUNCTYPE(None, ctypes.c_int32, ctypes.POINTER(ctypes.c_double), ctypes.c_double,
@@ -127,6 +128,8 @@ def load() -> ctypes.CDLL:
         "pr_get_topk": ([P, i32, P, P, P], ctypes.c_int),
         "pr_group_topk": ([P, i32, i32, P, P, P], ctypes.c_int),
         "pr_topk_merge": ([i32, P, P, P, i32, P, P, P], ctypes.c_int),
+        "pr_set_teleport": ([P, P], ctypes.c_int),
+        "pr_set_teleport_sparse": ([P, i32, P, P, dbl], ctypes.c_int),
         # internal (not in the header): pr_get_topk with the narrowing threshold and the pass counts
         "pr_topk_select_ex": ([P, i32, i64, P, P, P, P], ctypes.c_int),
     }

@@ -2,7 +2,7 @@
 
 CLI: ``python -m sparky_hip <input-path> [iterations=10] [--format edges|ccjson]
 [--out DIR] [--save-every-iter] [--dangling=local|none] [--device N] [--quiet]
-[--resume DIR/PageRank<i>] [--devices D0,D1,...] [--top K]``
+[--resume DIR/PageRank<i>] [--devices D0,D1,...] [--top K] [--seeds FILE]``
 
 * input: text edge list, ``src dst`` per line; a single-token line ``src`` is a record without
   ``a`` links (Sparky.java:114-118).  Tokens (URLs) are taken verbatim and interned to dense
@@ -19,6 +19,12 @@ CLI: ``python -m sparky_hip <input-path> [iterations=10] [--form
 * ``--top K``: the final listing is only the K highest-ranked URLs -- rank descending, ties by
   first appearance (ID ascending) -- selected on the GPU (``PageRankGraph.topk`` /
   ``PartGroup.topk``); without ``--out`` the rank vector never crosses to the host.
+* ``--seeds FILE``: personalised PageRank.  One ``url`` or ``url weight`` per line (weight > 0,
+  default 1; blank and ``#`` lines skipped): the teleport mass 0.15 N goes to the seeds in
+  proportion to their weights, every other URL's teleport term is 0 (``prh_seed_teleport``, then
+  ``set_teleport_sparse``); the dangling term stays uniform.  The file is read and checked before
+  the graph is created: a bad one exits with status 2 without touching a GPU.  Same outputs as the
+  C++ CLI: ``pagerank edges.txt 20 --seeds seeds.txt --top 100``.
 """
 from __future__ import annotations
 
@@ -136,7 +142,7 @@ def saved_iteration(path: str) -> int:
     return -1
 
 
-def _run_group(edges, devices, dangling, n_run, init, cb, want_ranks, top=0):
+def _run_group(edges, devices, dangling, n_run, init, cb, want_ranks, top=0, seeds=None):
     """--devices: one part per listed device, one process (pr_group_*); the callback gets the
     merged ranks of every part after each iteration, as with PageRankGraph.run.  Returns the
     final ranks, or with top > 0 the (ids, ranks) of PartGroup.topk(top)."""
@@ -147,6 +153,8 @@ def _run_group(edges, devices, dangling, n_run, init, cb, want_ranks, top=0):
             parts.append(PageRankGraph(edges.n_vertices, edges.src, edges.dst, device=d, dangling=dangling,
                                        keep_canonical=False, part=p, n_parts=P))
         grp = PartGroup(parts)
+        if seeds is not None:
+            grp.set_teleport_sparse(*seeds)
         grp.reset(init_ranks=init)
         for it in range(n_run):
             grp.step(1)
@@ -159,7 +167,7 @@ def _run_group(edges, devices, dangling, n_run, init, cb, want_ranks, top=0):
 
 
 def main(argv=None) -> int:
-    from ._host import HostEdges
+    from ._host import HostEdges, HostError, seed_teleport
 
     ap = argparse.ArgumentParser(prog="sparky_hip", description=__doc__.splitlines()[0])
     ap.add_argument("edge_list")
@@ -175,6 +183,8 @@ def main(argv=None) -> int:
                     help="one row part per listed GPU (a device may repeat), one process (pr_group_*)")
     ap.add_argument("--top", type=int, default=None, metavar="K",
                     help="list only the K highest-ranked URLs (selected on the GPU)")
+    ap.add_argument("--seeds", default=None, metavar="FILE",
+                    help="personalised PageRank: seed URLs, one 'url' or 'url weight' per line")
     a = ap.parse_args(argv)
     if a.top is not None and a.top < 1:
         ap.error("--top takes a count K >= 1")
@@ -186,6 +196,15 @@ def main(argv=None) -> int:
         except ValueError:
             ap.error("--devices takes a comma-separated list of device numbers")
     edges = HostEdges.read(a.edge_list, a.format)  # native front-end + first-appearance interning
+    seeds = None
+    if a.seeds is not None:  # read and checked before any graph exists
+        try:
+            ids, weights = edges.read_seeds(a.seeds)
+        except HostError as e:
+            sys.stderr.write(f"sparky_hip: --seeds: {e}\n")
+            edges.close()
+            return 2
+        seeds = (ids, seed_teleport(weights, edges.n_vertices))  # the native expression: the C++ CLI's bits
     out = sys.stdout
     init, start = None, 0
     if a.resume:
@@ -206,6 +225,8 @@ def main(argv=None) -> int:
     if len(devices) == 1:
         with PageRankGraph(edges.n_vertices, edges.src, edges.dst, device=devices[0], dangling=a.dangling,
                            keep_canonical=False) as g:
+            if seeds is not None:
+                g.set_teleport_sparse(*seeds)
             if top and not a.out:  # no part file: the ranks stay on the device
                 g.reset(init_ranks=init)
                 for it in range(n_run):
@@ -216,7 +237,7 @@ def main(argv=None) -> int:
             if top:
                 ranks = g.topk(top)
     else:
-        ranks = _run_group(edges, devices, a.dangling, n_run, init, cb, bool(a.out), top)
+        ranks = _run_group(edges, devices, a.dangling, n_run, init, cb, bool(a.out), top, seeds)
     out.flush()
     if not a.quiet and top:
         edges.write_has_rank_ids(None, *ranks)

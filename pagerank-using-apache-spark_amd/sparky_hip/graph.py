@@ -51,6 +51,24 @@ def _init_array(init_ranks, n_vertices: int):
     return init
 
 
+def _teleport_array(teleport, n_vertices: int):
+    """teleport as a contiguous float64[V] (the C side reads exactly V doubles), or None."""
+    if teleport is None:
+        return None
+    t = np.ascontiguousarray(teleport, dtype=np.float64)
+    if t.shape != (n_vertices,):
+        raise ValueError(f"teleport must have shape ({n_vertices},), got {t.shape}")
+    return t
+
+
+def _sparse_arrays(ids, values):
+    i = np.ascontiguousarray(ids, dtype=np.int32)
+    v = np.ascontiguousarray(values, dtype=np.float64)
+    if i.ndim != 1 or i.shape != v.shape:
+        raise ValueError("ids and values must be 1-D arrays of the same length")
+    return i, v
+
+
 def device_count() -> int:
     n = ctypes.c_int32(0)
     check(_lib.load().pr_device_count(ctypes.byref(n)))
@@ -202,6 +220,21 @@ class PageRankGraph:
         check(_lib.load().pr_get_ranks(self._h, _ptr(out)))
         return out[: self.n_vertices]
 
+    def set_teleport(self, teleport) -> None:
+        """pr_set_teleport: personalised PageRank.  ``teleport`` is float64[V] in original-ID order,
+        the teleport *term* of every vertex (r' = t + damping * (S + dc / N); all 0.15 is the
+        scalar run, bitwise), or None: back to the scalar.  The vector belongs to the handle: it
+        survives reset() and run(), and holds from the next step on.  A part keeps its own rows:
+        call it on every part with the same vector (PartGroup.set_teleport does)."""
+        t = _teleport_array(teleport, self.n_vertices)
+        check(_lib.load().pr_set_teleport(self._h, _ptr(t)))
+
+    def set_teleport_sparse(self, ids, values, rest: float = 0.0) -> None:
+        """pr_set_teleport_sparse: t[ids[i]] = values[i], every other vertex ``rest``; the IDs must
+        be distinct and in [0, V)."""
+        i, v = _sparse_arrays(ids, values)
+        check(_lib.load().pr_set_teleport_sparse(self._h, int(i.shape[0]), _ptr(i), _ptr(v), float(rest)))
+
     def topk(self, k: int):
         """pr_get_topk: the k highest-ranked vertices of this part, selected on the device -- rank
         descending, ties by original ID ascending.  Returns (ids int32[n], ranks float64[n]) with
@@ -346,6 +379,18 @@ class PartGroup:
         for p in self.parts:
             p.ranks(out)
         return out[:V]
+
+    def set_teleport(self, teleport) -> None:
+        """PageRankGraph.set_teleport on every part (the call is local to a part, not collective)."""
+        t = _teleport_array(teleport, self.parts[0].n_vertices)
+        for p in self.parts:
+            p.set_teleport(t)
+
+    def set_teleport_sparse(self, ids, values, rest: float = 0.0) -> None:
+        """PageRankGraph.set_teleport_sparse on every part."""
+        i, v = _sparse_arrays(ids, values)
+        for p in self.parts:
+            p.set_teleport_sparse(i, v, rest)
 
     def topk(self, k: int):
         """pr_group_topk: every part's top-K list, merged; (ids int32[n], ranks float64[n])."""

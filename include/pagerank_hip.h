@@ -271,6 +271,53 @@ int pr_group_topk(pr_graph *const *parts, int32_t n_parts, int32_t k, int32_t *i
 
 void pr_graph_destroy(pr_graph *g);
 
+/* ---- batched personalised PageRank ---------------------------------------------------- */
+/* A batch advances `width` (1..16) rank vectors over one graph together: every column j has its
+ * own teleport vector and runs exactly the personalised iteration documented at pr_set_teleport,
+ * r'_j[v] = t_j[v] + damping * (S_j[v] + dc_j / N) with rounded add / multiply / divide, S_j = r_old_j
+ * for rows without in-links, dc_j = the sum of column j's ranks over the vertices the graph treats
+ * as dangling (0 under PR_DANGLING_NONE), ranks never normalised.  The columns are stored
+ * interleaved (stride = the next power of two >= width), so one pass streams the column indices
+ * once for all of them and every gather fetches 8 * stride contiguous bytes.  A column without a
+ * vector uses the scalar `teleport` of pr_batch_reset (the plain Sparky run); a column's vector
+ * survives pr_batch_reset and is cleared by pr_batch_set_teleport(b, column, NULL).  Every sum has
+ * a fixed order that depends on the graph and the stride only: two runs agree bitwise, a column's
+ * bits do not depend on its position or on its neighbours.  Against pr_step with the same vector the
+ * ranks agree to rounding (the orders of summation differ), not bitwise.
+ * Scope (each an error, not a fallback): the graph must be a single part (n_parts == 1, not in a
+ * pr_group_*, no communicator) and must have kept its canonical CSR (no PR_NO_CANONICAL), else
+ * PR_ERR_STATE.  The batch runs over that canonical CSR in original IDs with kernels, a stream and
+ * state of its own; it only reads the graph's buffers, so the graph's own iteration and its
+ * PR_INFO_DEVICE_BYTES are unaffected (the batch reports its bytes through pr_batch_info).  The
+ * batch borrows the graph: destroy the batch first.  A pr_batch handle is not re-entrant.
+ * Errors of the setters match pr_set_teleport*: a NULL batch, a column outside [0, width), an ID
+ * outside [0, V), a duplicate ID, a non-finite value: PR_ERR_INVALID, checked on the host before any
+ * device call, nothing changed.  pr_batch_step / get_* before pr_batch_reset: PR_ERR_STATE. */
+typedef struct pr_batch pr_batch;
+int pr_batch_create(pr_graph *g, int32_t width, pr_batch **out); /* 1 <= width <= 16 */
+/* V doubles in original-ID order, or NULL: back to the scalar.  Waits for the enqueued steps. */
+int pr_batch_set_teleport(pr_batch *b, int32_t column, const double *teleport);
+/* t[ids[i]] = values[i], every other vertex `rest`; bitwise the equivalent dense vector. */
+int pr_batch_set_teleport_sparse(pr_batch *b, int32_t column, int32_t n, const int32_t *ids,
+                                 const double *values, double rest);
+/* init_ranks: NULL (1.0) or V doubles, used for every column. */
+int pr_batch_reset(pr_batch *b, double teleport, double damping, const double *init_ranks);
+/* Enqueues `iterations` iterations of every column; no host sync between iterations. */
+int pr_batch_step(pr_batch *b, int32_t iterations);
+int pr_batch_sync(pr_batch *b);
+/* Column `column`: V doubles in original-ID order.  Waits for the enqueued steps. */
+int pr_batch_get_ranks(pr_batch *b, int32_t column, double *ranks_out);
+/* `width` doubles each: per column the dc used by the last iteration and its L1 delta. */
+int pr_batch_get_norms(pr_batch *b, double *dc_out, double *l_out);
+/* pr_get_topk over one column (same order, same exact ties, same bits as pr_batch_get_ranks). */
+int pr_batch_get_topk(pr_batch *b, int32_t column, int32_t k, int32_t *ids_out, double *ranks_out,
+                      int32_t *n_out);
+/* info[i] for i < min(n_info, 7): width, stride, work units, rows split over several units,
+ * device bytes held by the batch, iterations done since the last reset, HIP-event time in ns of
+ * the iterations of the last pr_batch_step call (-1: none yet, or they are still running). */
+int pr_batch_info(const pr_batch *b, int64_t *info, int32_t n_info);
+void pr_batch_destroy(pr_batch *b);
+
 /* ---- synthetic inputs and device-side interning (benchmark front-end) ----------------- */
 /* R-MAT (Graph500 parameters a,b,c, d = 1-a-b-c), n_edges edges over 2^scale labels, labels
  * scrambled by a seeded bijection.  d_src/d_dst: device arrays of n_edges int32. */

@@ -1,0 +1,601 @@
+// Batched personalised PageRank for gfx950 (pr_batch_*; planner arithmetic in pr_batch.h): up to
+// 16 rank vectors advance together over the graph's canonical CSR (original IDs), so the column
+// indices are streamed once for all of them and every gather fetches 8 * stride contiguous bytes.
+//
+// Storage: R (ranks), T (teleport terms) and two C buffers (contributions c = r / out_deg,
+// double-buffered) are V x stride doubles, element (v, j) at v * stride + j; stride = the next
+// power of two >= width.  Padding columns hold zeros and stay zero; no result reads them.
+//
+// One iteration is three launches on the batch's stream, with no host sync in between:
+//   k_batch_units     one wave per work unit (pr_batch.h): lane = g * stride + j, the 64 / stride
+//                     groups each take one in-link per step -- a group's lanes share one canon_col
+//                     load and read C[col * stride + j] -- and the group sums are combined by a
+//                     fixed butterfly; rows of at most kBatchShortRow in-links are taken one
+//                     group per row, G rows at a time, instead.  A PACK unit keeps its rows' sums in LDS and then updates
+//                     rows x stride elements with all 64 lanes (affine update, c' = r' / out_deg,
+//                     per-column dangling and L1 partials); a CHUNK unit stores its partial sum.
+//   k_batch_long      adds the chunk partials of every long row in chunk order and updates it.
+//   k_batch_finalize  reduces the per-workgroup partials in fixed order into dc[0..stride) and
+//                     l1[0..stride) in device memory, where the next iteration reads dc.
+// Units are dealt to the waves of a fixed grid (unit u -> wave u % grid), so every sum -- a row's,
+// a column's dangling mass -- has an order that depends on the graph and the stride only.  No
+// floating-point atomics anywhere.
+//
+// The batch only reads the graph's canon_* buffers; it launches none of the graph's kernels and
+// owns its stream and all its state.
+#include <algorithm>
+#include <cmath>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "pr_batch.h"
+#include "pr_device.h"
+#include "pr_graph.h"
+
+struct pr_batch {
+  pr_graph *g = nullptr;  // borrowed: destroy the batch first
+  int device = 0;
+  hipStream_t stream = nullptr;
+  int width = 0, stride = 0;
+  int32_t V = 0;
+  bool dangling_none = false;
+  int64_t n_units = 0, n_long = 0, n_slots = 0;
+  int ugrid = 1, lgrid = 0;  // workgroups of k_batch_units / k_batch_long
+  pr::DevBuf units, long_row, long_p0, chunk_part;
+  pr::DevBuf R, T, C[2];
+  pr::DevBuf dc[2], l1;  // stride doubles each; dc[cur] is what the next iteration reads
+  pr::DevBuf part;       // per workgroup: stride dangling partials, then stride L1 partials
+  pr::DevBuf colbuf;     // V doubles: one column, extracted (ranks, top-K) or on its way into T
+  pr::TopkState *topk = nullptr;
+  uint32_t vec_mask = 0;  // columns with a teleport vector set
+  double teleport = 0.15, damping = 0.85;
+  int cur = 0;
+  int64_t iters_done = 0;
+  bool ready = false;
+  // HIP events around the iterations of the last pr_batch_step call (pr_batch_info reports the time)
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  bool timed = false;
+
+  size_t device_bytes() const {
+    return units.bytes + long_row.bytes + long_p0.bytes + chunk_part.bytes + R.bytes + T.bytes + C[0].bytes +
+           C[1].bytes + dc[0].bytes + dc[1].bytes + l1.bytes + part.bytes + colbuf.bytes + pr::topk_state_bytes(topk);
+  }
+};
+
+namespace pr {
+namespace {
+
+constexpr int kBatchGridMax = 8192;  // waves of k_batch_units (a constant: sums must not depend on the device)
+constexpr int kBatchThreads = 256;   // the element-wise kernels
+
+struct BatchArgs {
+  const BatchUnit *units;
+  int64_t n_units;
+  const int64_t *rowptr;
+  const int32_t *col, *deg;
+  const uint8_t *vflags;
+  const double *cin;
+  double *cout, *r;
+  const double *t, *dc;
+  double *chunk_part, *part;
+  double n_vertices, damping;
+  int dangling_none;
+};
+
+__device__ __forceinline__ double batch_affine(double S, double tdc, double teleport, double damping) {
+  return __dadd_rn(teleport, __dmul_rn(damping, __dadd_rn(S, tdc)));
+}
+
+// Butterfly over the lane groups of a wave: every lane ends with the sum over the lanes that share
+// its column, combined in one fixed order.
+template <int S>
+__device__ __forceinline__ double group_sum(double x) {
+#pragma unroll
+  for (int off = S; off < kWave; off <<= 1) x = __dadd_rn(x, __shfl_xor(x, off, kWave));
+  return x;
+}
+
+// Column j's sum over in-links [b, e): group g adds b + g, b + g + G, ... in that order (four
+// gathers in flight at a time), then the groups are combined.  Valid in every lane.
+template <int S>
+__device__ __forceinline__ double row_sum(const int32_t *__restrict__ col, const double *__restrict__ cin, int64_t b,
+                                          int64_t e, int g, int j) {
+  constexpr int G = kWave / S;
+  double acc = 0.0;
+  int64_t i = b + g;
+  for (; i + 3 * G < e; i += 4 * G) {
+    const int32_t c0 = col[i], c1 = col[i + G], c2 = col[i + 2 * G], c3 = col[i + 3 * G];
+    const double x0 = cin[(int64_t)c0 * S + j], x1 = cin[(int64_t)c1 * S + j];
+    const double x2 = cin[(int64_t)c2 * S + j], x3 = cin[(int64_t)c3 * S + j];
+    acc = __dadd_rn(__dadd_rn(__dadd_rn(__dadd_rn(acc, x0), x1), x2), x3);
+  }
+  for (; i < e; i += G) acc = __dadd_rn(acc, cin[(int64_t)col[i] * S + j]);
+  return group_sum<S>(acc);
+}
+
+// Element (v, j) of a row whose in-link sum is Sv: the update, the new contribution and the
+// column's dangling / L1 partials.
+__device__ __forceinline__ void update_elem(const BatchArgs &a, int64_t v, int64_t p, double Sv, double rold,
+                                            uint32_t f, double tdc, double &dcp, double &l1p) {
+  const double rn = batch_affine(Sv, tdc, a.t[p], a.damping);
+  a.r[p] = rn;
+  const int32_t d = a.deg[v];
+  if (d > 0) a.cout[p] = __ddiv_rn(rn, (double)d);
+  else if ((f & PR_VF_SINK) && !a.dangling_none) dcp = __dadd_rn(dcp, rn);
+  l1p = __dadd_rn(l1p, fabs(rn - rold));
+}
+
+template <int S>
+__global__ __launch_bounds__(kWave) void k_batch_units(BatchArgs a) {
+  constexpr int G = kWave / S;
+  __shared__ double sS[kBatchUnitRows * S];
+  const int lane = threadIdx.x, g = lane / S, j = lane % S;
+  const double tdc = a.dc[j] / a.n_vertices;
+  double dcp = 0.0, l1p = 0.0;
+  for (int64_t u = blockIdx.x; u < a.n_units; u += gridDim.x) {
+    const BatchUnit un = a.units[u];
+    if (un.rows < 0) {  // CHUNK: the partial sum of one piece of a long row
+      const double acc = row_sum<S>(a.col, a.cin, un.e0, un.e0 + un.n, g, j);
+      if (lane < S) a.chunk_part[(int64_t)un.slot * S + j] = acc;
+      continue;
+    }
+    const int rows = un.rows;  // <= kBatchUnitRows = 64: lane k holds row k's first in-link
+    const long long rp_l = (long long)a.rowptr[(int64_t)un.row0 + (lane < rows ? lane : rows)];
+    const int64_t uend = un.e0 + un.n;
+    // short rows (1 .. kBatchShortRow in-links): one lane group per row, G rows at a time; all the
+    // row's gathers are in flight at once and are added in in-link order
+    for (int k0 = 0; k0 < rows; k0 += G) {
+      const int k = k0 + g;
+      const int ks = k < rows ? k : 0;
+      const int64_t b = __shfl(rp_l, ks, kWave);
+      const int64_t e1 = __shfl(rp_l, ks + 1 < kWave ? ks + 1 : kWave - 1, kWave);
+      const int64_t deg = k < rows ? (ks + 1 < rows ? e1 : uend) - b : 0;
+      if (deg > 0 && deg <= kBatchShortRow) {
+        int32_t c[kBatchShortRow];
+        double x[kBatchShortRow];
+#pragma unroll
+        for (int q = 0; q < kBatchShortRow; ++q) c[q] = q < deg ? a.col[b + q] : 0;
+#pragma unroll
+        for (int q = 0; q < kBatchShortRow; ++q) x[q] = q < deg ? a.cin[(int64_t)c[q] * S + j] : 0.0;
+        double acc = 0.0;
+#pragma unroll
+        for (int q = 0; q < kBatchShortRow; ++q)
+          if (q < deg) acc = __dadd_rn(acc, x[q]);
+        sS[k * S + j] = acc;
+      }
+    }
+    // longer rows: the whole wave per row
+    for (int k = 0; k < rows; ++k) {
+      const int64_t b = __shfl(rp_l, k, kWave);
+      const int64_t e = k + 1 < rows ? (int64_t)__shfl(rp_l, k + 1, kWave) : uend;
+      if (e - b <= kBatchShortRow) continue;  // done above, or empty: the update takes the old rank
+      const double acc = row_sum<S>(a.col, a.cin, b, e, g, j);
+      if (lane < S) sS[k * S + j] = acc;
+    }
+    __syncthreads();
+    const int total = rows * S;
+    for (int idx = lane; idx < total; idx += kWave) {  // idx % S == j: 64 is a multiple of S
+      const int64_t v = (int64_t)un.row0 + idx / S, p = v * S + j;
+      const uint32_t f = a.vflags[v];
+      const double rold = a.r[p];
+      update_elem(a, v, p, (f & PR_VF_INDEG0) ? rold : sS[idx], rold, f, tdc, dcp, l1p);
+    }
+    __syncthreads();
+  }
+  dcp = group_sum<S>(dcp);
+  l1p = group_sum<S>(l1p);
+  if (lane < S) {
+    a.part[((int64_t)blockIdx.x * 2) * S + j] = dcp;
+    a.part[((int64_t)blockIdx.x * 2 + 1) * S + j] = l1p;
+  }
+}
+
+// Per-column sums of a workgroup's (dcp, l1p) in thread order (thread t holds column t % S), stored
+// as workgroup `blk` of part.
+template <int S>
+__device__ __forceinline__ void block_col_part(double dcp, double l1p, double *__restrict__ part, int64_t blk) {
+  __shared__ double sh[2][kBatchThreads];
+  const int t = threadIdx.x;
+  sh[0][t] = dcp;
+  sh[1][t] = l1p;
+  __syncthreads();
+  if (t < S) {
+    double x = 0.0, y = 0.0;
+    for (int k = t; k < kBatchThreads; k += S) {
+      x = __dadd_rn(x, sh[0][k]);
+      y = __dadd_rn(y, sh[1][k]);
+    }
+    part[(blk * 2) * S + t] = x;
+    part[(blk * 2 + 1) * S + t] = y;
+  }
+}
+
+// One thread per (long row, column): the row's chunk partials in chunk order, then the update.
+template <int S>
+__global__ __launch_bounds__(kBatchThreads) void k_batch_long(BatchArgs a, const int32_t *__restrict__ long_row,
+                                                              const int32_t *__restrict__ long_p0, int64_t n_long,
+                                                              int64_t part_block0) {
+  const int64_t idx = (int64_t)blockIdx.x * kBatchThreads + threadIdx.x;
+  const int64_t q = idx / S;
+  const int j = threadIdx.x % S;
+  double dcp = 0.0, l1p = 0.0;
+  if (q < n_long) {
+    const int32_t p0 = long_p0[q], p1 = long_p0[q + 1];
+    double acc = 0.0;
+    for (int32_t k = p0; k < p1; ++k) acc = __dadd_rn(acc, a.chunk_part[(int64_t)k * S + j]);
+    const int64_t v = long_row[q], p = v * S + j;
+    update_elem(a, v, p, acc, a.r[p], a.vflags[v], a.dc[j] / a.n_vertices, dcp, l1p);
+  }
+  block_col_part<S>(dcp, l1p, a.part, part_block0 + blockIdx.x);
+}
+
+// Workgroup kind * S + j: column j's dangling (kind 0) or L1 (kind 1) partials of n_blocks
+// workgroups, in fixed order.
+__global__ __launch_bounds__(kBatchThreads) void k_batch_finalize(const double *__restrict__ part, int64_t n_blocks,
+                                                                  int S, double *__restrict__ dc_out,
+                                                                  double *__restrict__ l1_out) {
+  __shared__ double red[kBatchThreads / kWave];
+  const int kind = blockIdx.x / S, j = blockIdx.x % S;
+  double acc = 0.0;
+  for (int64_t b = threadIdx.x; b < n_blocks; b += kBatchThreads) acc = __dadd_rn(acc, part[(b * 2 + kind) * S + j]);
+  acc = block_sum<kBatchThreads>(acc, red);
+  if (threadIdx.x == 0) (kind ? l1_out : dc_out)[j] = acc;
+}
+
+// Ranks to init (or 1.0) in every column, the scalar teleport into the columns without a vector,
+// the contributions of those ranks, zeros into the padding columns; per-workgroup dangling partials.
+// gridDim.x * kBatchThreads is a multiple of S, so a thread stays in column threadIdx.x % S.
+template <int S>
+__global__ __launch_bounds__(kBatchThreads) void k_batch_reset(int64_t V, int width, const double *__restrict__ init,
+                                                               uint32_t vec_mask, double teleport,
+                                                               const int32_t *__restrict__ deg,
+                                                               const uint8_t *__restrict__ vflags, int dangling_none,
+                                                               double *__restrict__ r, double *__restrict__ t,
+                                                               double *__restrict__ c0, double *__restrict__ c1,
+                                                               double *__restrict__ part) {
+  const int j = threadIdx.x % S;
+  double dcp = 0.0;
+  for (int64_t p = (int64_t)blockIdx.x * kBatchThreads + threadIdx.x; p < V * S; p += (int64_t)gridDim.x * kBatchThreads) {
+    const int64_t v = p / S;
+    const double x = j < width ? (init ? init[v] : 1.0) : 0.0;
+    r[p] = x;
+    if (!((vec_mask >> j) & 1u)) t[p] = j < width ? teleport : 0.0;
+    const int32_t d = deg[v];
+    c0[p] = d > 0 ? __ddiv_rn(x, (double)d) : 0.0;
+    c1[p] = 0.0;
+    if (d == 0 && (vflags[v] & PR_VF_SINK) && !dangling_none) dcp = __dadd_rn(dcp, x);
+  }
+  block_col_part<S>(dcp, 0.0, part, blockIdx.x);
+}
+
+// Column j of m (V x S) from / to V contiguous doubles.
+__global__ __launch_bounds__(kBatchThreads) void k_batch_extract(int64_t V, int S, int j, const double *__restrict__ m,
+                                                                 double *__restrict__ out) {
+  for (int64_t v = (int64_t)blockIdx.x * kBatchThreads + threadIdx.x; v < V; v += (int64_t)gridDim.x * kBatchThreads)
+    out[v] = m[v * S + j];
+}
+__global__ __launch_bounds__(kBatchThreads) void k_batch_set_col(int64_t V, int S, int j, const double *__restrict__ in,
+                                                                 double value, double *__restrict__ m) {
+  for (int64_t v = (int64_t)blockIdx.x * kBatchThreads + threadIdx.x; v < V; v += (int64_t)gridDim.x * kBatchThreads)
+    m[v * S + j] = in ? in[v] : value;
+}
+
+struct BatchDeviceGuard {
+  int prev = -1;
+  explicit BatchDeviceGuard(int dev) {
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    (void)hipSetDevice(dev);
+  }
+  ~BatchDeviceGuard() {
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+};
+
+BatchArgs batch_args(const pr_batch *b) {
+  const pr_graph *g = b->g;
+  BatchArgs a{};
+  a.units = b->units.as<BatchUnit>();
+  a.n_units = b->n_units;
+  a.rowptr = g->canon_rowptr.as<int64_t>();
+  a.col = g->canon_col.as<int32_t>();
+  a.deg = g->canon_deg.as<int32_t>();
+  a.vflags = g->canon_vflags.as<uint8_t>();
+  a.cin = b->C[b->cur].as<double>();
+  a.cout = b->C[b->cur ^ 1].as<double>();
+  a.r = b->R.as<double>();
+  a.t = b->T.as<double>();
+  a.dc = b->dc[b->cur].as<double>();
+  a.chunk_part = b->chunk_part.as<double>();
+  a.part = b->part.as<double>();
+  a.n_vertices = (double)b->V;
+  a.damping = b->damping;
+  a.dangling_none = b->dangling_none ? 1 : 0;
+  return a;
+}
+
+template <int S>
+int launch_iteration(pr_batch *b) {
+  const BatchArgs a = batch_args(b);
+  hipLaunchKernelGGL(k_batch_units<S>, dim3(b->ugrid), dim3(kWave), 0, b->stream, a);
+  PR_HIP(hipGetLastError());
+  if (b->n_long > 0) {
+    hipLaunchKernelGGL(k_batch_long<S>, dim3(b->lgrid), dim3(kBatchThreads), 0, b->stream, a, b->long_row.as<int32_t>(),
+                       b->long_p0.as<int32_t>(), b->n_long, (int64_t)b->ugrid);
+    PR_HIP(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_batch_finalize, dim3(2 * S), dim3(kBatchThreads), 0, b->stream, b->part.as<double>(),
+                     (int64_t)b->ugrid + b->lgrid, S, b->dc[b->cur ^ 1].as<double>(), b->l1.as<double>());
+  PR_HIP(hipGetLastError());
+  return PR_OK;
+}
+
+template <int S>
+int launch_reset(pr_batch *b, const double *d_init) {
+  const pr_graph *g = b->g;
+  const unsigned grid = grid_for((int64_t)b->V * S, kBatchThreads, kBatchGridMax);
+  hipLaunchKernelGGL(k_batch_reset<S>, dim3(grid), dim3(kBatchThreads), 0, b->stream, (int64_t)b->V, b->width, d_init,
+                     b->vec_mask, b->teleport, g->canon_deg.as<int32_t>(), g->canon_vflags.as<uint8_t>(),
+                     b->dangling_none ? 1 : 0, b->R.as<double>(), b->T.as<double>(), b->C[0].as<double>(),
+                     b->C[1].as<double>(), b->part.as<double>());
+  PR_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_batch_finalize, dim3(2 * S), dim3(kBatchThreads), 0, b->stream, b->part.as<double>(),
+                     (int64_t)grid, S, b->dc[0].as<double>(), b->l1.as<double>());
+  PR_HIP(hipGetLastError());
+  return PR_OK;
+}
+
+#define PR_BATCH_DISPATCH(fn, b, ...)                                    \
+  ((b)->stride == 1   ? fn<1>(b, ##__VA_ARGS__)                          \
+   : (b)->stride == 2 ? fn<2>(b, ##__VA_ARGS__)                          \
+   : (b)->stride == 4 ? fn<4>(b, ##__VA_ARGS__)                          \
+   : (b)->stride == 8 ? fn<8>(b, ##__VA_ARGS__)                          \
+                      : fn<16>(b, ##__VA_ARGS__))
+
+// Column j of T: V doubles from the host (through colbuf), or `value` everywhere (host == nullptr).
+int upload_column(pr_batch *b, int j, const double *host, double value) {
+  PR_HIP(hipStreamSynchronize(b->stream));  // the enqueued steps still read T
+  if (host && b->V > 0)
+    PR_HIP(hipMemcpyAsync(b->colbuf.p, host, sizeof(double) * (size_t)b->V, hipMemcpyHostToDevice, b->stream));
+  hipLaunchKernelGGL(k_batch_set_col, dim3(grid_for(b->V, kBatchThreads, 4096)), dim3(kBatchThreads), 0, b->stream,
+                     (int64_t)b->V, b->stride, j, host ? b->colbuf.as<double>() : nullptr, value, b->T.as<double>());
+  PR_HIP(hipGetLastError());
+  PR_HIP(hipStreamSynchronize(b->stream));  // `host` is borrowed for the call only
+  return PR_OK;
+}
+
+int extract_column(pr_batch *b, int j) {
+  hipLaunchKernelGGL(k_batch_extract, dim3(grid_for(b->V, kBatchThreads, 4096)), dim3(kBatchThreads), 0, b->stream,
+                     (int64_t)b->V, b->stride, j, b->R.as<double>(), b->colbuf.as<double>());
+  PR_HIP(hipGetLastError());
+  return PR_OK;
+}
+
+int check_column(const pr_batch *b, int32_t column) {
+  if (!b) return fail(PR_ERR_INVALID, "NULL batch");
+  if (column < 0 || column >= b->width)
+    return fail(PR_ERR_INVALID, "column " + std::to_string(column) + " is outside [0, width)");
+  return PR_OK;
+}
+
+int build_batch(pr_batch *b) {
+  pr_graph *g = b->g;
+  const int S = b->stride;
+  const size_t V = (size_t)b->V;
+  PR_HIP(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+  PR_HIP(hipEventCreate(&b->ev0));
+  PR_HIP(hipEventCreate(&b->ev1));
+  std::vector<int64_t> rp(V + 1, 0);
+  PR_HIP(hipStreamSynchronize(g->stream));
+  PR_HIP(hipMemcpy(rp.data(), g->canon_rowptr.p, sizeof(int64_t) * (V + 1), hipMemcpyDeviceToHost));
+  BatchPlan plan;
+  batch_plan(rp.data(), (int64_t)V, S, &plan);
+  b->n_units = (int64_t)plan.units.size();
+  b->n_long = (int64_t)plan.long_row.size();
+  b->n_slots = plan.long_p0.back();
+  b->ugrid = (int)std::max<int64_t>(1, std::min<int64_t>(b->n_units, kBatchGridMax));
+  b->lgrid = (int)((b->n_long * S + kBatchThreads - 1) / kBatchThreads);
+  PR_TRY(b->units.alloc(sizeof(BatchUnit) * plan.units.size()));
+  PR_TRY(b->long_row.alloc(sizeof(int32_t) * plan.long_row.size()));
+  PR_TRY(b->long_p0.alloc(sizeof(int32_t) * plan.long_p0.size()));
+  PR_TRY(b->chunk_part.alloc(sizeof(double) * (size_t)b->n_slots * S));
+  if (!plan.units.empty())
+    PR_HIP(hipMemcpy(b->units.p, plan.units.data(), sizeof(BatchUnit) * plan.units.size(), hipMemcpyHostToDevice));
+  if (!plan.long_row.empty())
+    PR_HIP(hipMemcpy(b->long_row.p, plan.long_row.data(), sizeof(int32_t) * plan.long_row.size(), hipMemcpyHostToDevice));
+  PR_HIP(hipMemcpy(b->long_p0.p, plan.long_p0.data(), sizeof(int32_t) * plan.long_p0.size(), hipMemcpyHostToDevice));
+  const size_t mat = sizeof(double) * V * (size_t)S;
+  PR_TRY(b->R.alloc(mat));
+  PR_TRY(b->T.alloc(mat));
+  PR_TRY(b->C[0].alloc(mat));
+  PR_TRY(b->C[1].alloc(mat));
+  PR_TRY(b->dc[0].alloc(sizeof(double) * S));
+  PR_TRY(b->dc[1].alloc(sizeof(double) * S));
+  PR_TRY(b->l1.alloc(sizeof(double) * S));
+  // the reset's grid is at most kBatchGridMax workgroups, an iteration's ugrid + lgrid
+  PR_TRY(b->part.alloc(sizeof(double) * 2 * S * ((size_t)kBatchGridMax + (size_t)b->lgrid)));
+  PR_TRY(b->colbuf.alloc(sizeof(double) * V));
+  return PR_OK;
+}
+
+}  // namespace
+}  // namespace pr
+
+using pr::fail;
+
+extern "C" {
+
+int pr_batch_create(pr_graph *g, int32_t width, pr_batch **out) {
+  if (!g || !out) return fail(PR_ERR_INVALID, "NULL argument");
+  *out = nullptr;
+  if (width < 1 || width > pr::kBatchMaxWidth) return fail(PR_ERR_INVALID, "width must be in [1, 16]");
+  if (g->nparts != 1 || g->grouped || g->comm)
+    return fail(PR_ERR_STATE, "a batch needs a single-part graph (no group, no communicator)");
+  if (!g->has_canonical) return fail(PR_ERR_STATE, "a batch needs the canonical CSR (graph built with PR_NO_CANONICAL)");
+  pr::BatchDeviceGuard dg(g->device);
+  pr_batch *b = new (std::nothrow) pr_batch();
+  if (!b) return fail(PR_ERR_OOM, "host allocation failed");
+  b->g = g;
+  b->device = g->device;
+  b->width = width;
+  b->stride = pr::batch_stride(width);
+  b->V = g->V;
+  b->dangling_none = (g->flags & PR_DANGLING_NONE) != 0;
+  const int rc = pr::build_batch(b);
+  if (rc != PR_OK) {
+    const std::string msg = pr_last_error();
+    pr_batch_destroy(b);
+    pr::set_error(msg);
+    return rc;
+  }
+  *out = b;
+  return PR_OK;
+}
+
+int pr_batch_set_teleport(pr_batch *b, int32_t column, const double *teleport) {
+  PR_TRY(pr::check_column(b, column));
+  if (teleport)  // host checks first: nothing below touches the device before they pass
+    for (int32_t v = 0; v < b->V; ++v)
+      if (!std::isfinite(teleport[v])) return fail(PR_ERR_INVALID, "teleport[" + std::to_string(v) + "] is not finite");
+  pr::BatchDeviceGuard dg(b->device);
+  PR_TRY(pr::upload_column(b, column, teleport, b->teleport));
+  if (teleport) b->vec_mask |= 1u << column;
+  else b->vec_mask &= ~(1u << column);
+  return PR_OK;
+}
+
+int pr_batch_set_teleport_sparse(pr_batch *b, int32_t column, int32_t n, const int32_t *ids, const double *values,
+                                 double rest) {
+  PR_TRY(pr::check_column(b, column));
+  if (n < 0) return fail(PR_ERR_INVALID, "n < 0");
+  if (n > 0 && (!ids || !values)) return fail(PR_ERR_INVALID, "NULL argument");
+  if (!std::isfinite(rest)) return fail(PR_ERR_INVALID, "rest is not finite");
+  for (int32_t i = 0; i < n; ++i) {
+    if (ids[i] < 0 || ids[i] >= b->V)
+      return fail(PR_ERR_INVALID, "ids[" + std::to_string(i) + "] = " + std::to_string(ids[i]) + " is outside [0, V)");
+    if (!std::isfinite(values[i])) return fail(PR_ERR_INVALID, "values[" + std::to_string(i) + "] is not finite");
+  }
+  std::vector<double> dense((size_t)b->V, rest);
+  std::vector<uint8_t> seen((size_t)b->V, 0);
+  for (int32_t i = 0; i < n; ++i) {
+    if (seen[(size_t)ids[i]]) return fail(PR_ERR_INVALID, "vertex " + std::to_string(ids[i]) + " is listed twice in ids");
+    seen[(size_t)ids[i]] = 1;
+    dense[(size_t)ids[i]] = values[i];
+  }
+  pr::BatchDeviceGuard dg(b->device);
+  PR_TRY(pr::upload_column(b, column, dense.data(), 0.0));
+  b->vec_mask |= 1u << column;
+  return PR_OK;
+}
+
+int pr_batch_reset(pr_batch *b, double teleport, double damping, const double *init_ranks) {
+  if (!b) return fail(PR_ERR_INVALID, "NULL batch");
+  pr::BatchDeviceGuard dg(b->device);
+  PR_HIP(hipStreamSynchronize(b->stream));
+  b->teleport = teleport;
+  b->damping = damping;
+  const double *d_init = nullptr;
+  if (init_ranks && b->V > 0) {
+    PR_HIP(hipMemcpyAsync(b->colbuf.p, init_ranks, sizeof(double) * (size_t)b->V, hipMemcpyHostToDevice, b->stream));
+    d_init = b->colbuf.as<double>();
+  }
+  PR_TRY(PR_BATCH_DISPATCH(pr::launch_reset, b, d_init));
+  PR_HIP(hipStreamSynchronize(b->stream));  // init_ranks is borrowed for the call only
+  b->cur = 0;
+  b->iters_done = 0;
+  b->ready = true;
+  return PR_OK;
+}
+
+int pr_batch_step(pr_batch *b, int32_t iterations) {
+  if (!b || iterations < 0) return fail(PR_ERR_INVALID, "NULL batch or iterations < 0");
+  if (!b->ready) return fail(PR_ERR_STATE, "pr_batch_step before pr_batch_reset");
+  pr::BatchDeviceGuard dg(b->device);
+  if (iterations > 0) PR_HIP(hipEventRecord(b->ev0, b->stream));
+  for (int32_t it = 0; it < iterations; ++it) {
+    PR_TRY(PR_BATCH_DISPATCH(pr::launch_iteration, b));
+    b->cur ^= 1;
+    ++b->iters_done;
+  }
+  if (iterations > 0) {
+    PR_HIP(hipEventRecord(b->ev1, b->stream));
+    b->timed = true;
+  }
+  return PR_OK;
+}
+
+int pr_batch_sync(pr_batch *b) {
+  if (!b) return fail(PR_ERR_INVALID, "NULL batch");
+  pr::BatchDeviceGuard dg(b->device);
+  PR_HIP(hipStreamSynchronize(b->stream));
+  return PR_OK;
+}
+
+int pr_batch_get_ranks(pr_batch *b, int32_t column, double *ranks_out) {
+  PR_TRY(pr::check_column(b, column));
+  if (!ranks_out) return fail(PR_ERR_INVALID, "NULL argument");
+  if (!b->ready) return fail(PR_ERR_STATE, "pr_batch_get_ranks before pr_batch_reset");
+  pr::BatchDeviceGuard dg(b->device);
+  PR_TRY(pr::extract_column(b, column));
+  if (b->V > 0)
+    PR_HIP(hipMemcpyAsync(ranks_out, b->colbuf.p, sizeof(double) * (size_t)b->V, hipMemcpyDeviceToHost, b->stream));
+  PR_HIP(hipStreamSynchronize(b->stream));
+  return PR_OK;
+}
+
+int pr_batch_get_norms(pr_batch *b, double *dc_out, double *l_out) {
+  if (!b || !dc_out || !l_out) return fail(PR_ERR_INVALID, "NULL argument");
+  if (!b->ready) return fail(PR_ERR_STATE, "pr_batch_get_norms before pr_batch_reset");
+  pr::BatchDeviceGuard dg(b->device);
+  double dc[pr::kBatchMaxWidth], l1[pr::kBatchMaxWidth];
+  // the dc *used* by the last iteration lives in the previous buffer (none run: the reset's)
+  const pr::DevBuf &used = b->dc[b->iters_done > 0 ? b->cur ^ 1 : b->cur];
+  PR_HIP(hipMemcpyAsync(dc, used.p, sizeof(double) * b->stride, hipMemcpyDeviceToHost, b->stream));
+  PR_HIP(hipMemcpyAsync(l1, b->l1.p, sizeof(double) * b->stride, hipMemcpyDeviceToHost, b->stream));
+  PR_HIP(hipStreamSynchronize(b->stream));
+  for (int j = 0; j < b->width; ++j) {
+    dc_out[j] = dc[j];
+    l_out[j] = b->iters_done > 0 ? l1[j] : 0.0;
+  }
+  return PR_OK;
+}
+
+int pr_batch_get_topk(pr_batch *b, int32_t column, int32_t k, int32_t *ids_out, double *ranks_out, int32_t *n_out) {
+  PR_TRY(pr::check_column(b, column));
+  if (k < 0) return fail(PR_ERR_INVALID, "k < 0");
+  if (!n_out || (k > 0 && (!ids_out || !ranks_out))) return fail(PR_ERR_INVALID, "NULL argument");
+  if (!b->ready) return fail(PR_ERR_STATE, "pr_batch_get_topk before pr_batch_reset");
+  pr::BatchDeviceGuard dg(b->device);
+  PR_TRY(pr::extract_column(b, column));
+  return pr::topk_select(&b->topk, b->device, b->stream, b->colbuf.as<double>(), nullptr, b->V, b->V, k,
+                         pr::kTopkNarrowDiv, ids_out, ranks_out, n_out, nullptr);
+}
+
+int pr_batch_info(const pr_batch *b, int64_t *info, int32_t n_info) {
+  if (!b || !info) return fail(PR_ERR_INVALID, "NULL argument");
+  int64_t step_ns = -1;  // the last pr_batch_step call's iterations, HIP events; -1: none yet or still running
+  float ms = 0.f;
+  if (n_info > 6 && b->timed) {
+    if (hipEventElapsedTime(&ms, b->ev0, b->ev1) == hipSuccess) step_ns = (int64_t)((double)ms * 1e6);
+    else (void)hipGetLastError();
+  }
+  const int64_t v[7] = {b->width, b->stride, b->n_units, b->n_long, (int64_t)b->device_bytes(), b->iters_done, step_ns};
+  for (int32_t i = 0; i < n_info && i < 7; ++i) info[i] = v[i];
+  return PR_OK;
+}
+
+void pr_batch_destroy(pr_batch *b) {
+  if (!b) return;
+  pr::BatchDeviceGuard dg(b->device);
+  if (b->stream) (void)hipStreamSynchronize(b->stream);
+  pr::topk_state_free(b->topk);
+  b->topk = nullptr;
+  if (b->ev0) (void)hipEventDestroy(b->ev0);
+  if (b->ev1) (void)hipEventDestroy(b->ev1);
+  hipStream_t s = b->stream;
+  b->stream = nullptr;
+  delete b;  // DevBufs free their memory
+  if (s) (void)hipStreamDestroy(s);
+}
+
+}  // extern "C"

@@ -273,4 +273,13 @@ int topk_part(pr_graph *g, int64_t k, int64_t narrow_div, int32_t *ids_out, doub
               int32_t *info);
 size_t topk_bytes(const pr_graph *g);  // device memory the query holds (0 before the first call)
 void topk_destroy(pr_graph *g);
+// The select behind topk_part, over any device rank array (pr_batch.hip runs it over an extracted
+// column): n_rows rows of r, oid[row] = original ID or -1 for a hole (nullptr: row = ID, no holes),
+// n_owned of them not holes; waits for s first.  *state (scratch) is created on first use; the
+// caller accounts for topk_state_bytes and frees it with topk_state_free.
+int topk_select(TopkState **state, int device, hipStream_t s, const double *r, const int32_t *oid, int64_t n_rows,
+                int64_t n_owned, int64_t k, int64_t narrow_div, int32_t *ids_out, double *ranks_out, int32_t *n_out,
+                int32_t *info);
+size_t topk_state_bytes(const TopkState *t);
+void topk_state_free(TopkState *t);
 }  // namespace pr

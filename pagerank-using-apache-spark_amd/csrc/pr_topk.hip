@@ -64,17 +64,17 @@ __device__ __forceinline__ void wave_hist_add(uint32_t *hw, bool valid, uint32_t
 }
 
 // Elements 2i and 2i + 1 of the rows (rank, original ID) as composite keys; ok = not a hole and
-// inside [0, n).  16 bytes per lane of r, 8 of oid.
+// inside [0, n).  16 bytes per lane of r, 8 of oid.  oid == nullptr: the identity map (row = ID).
 __device__ __forceinline__ void load_rows2(const double *__restrict__ r, const int32_t *__restrict__ oid,
                                            int64_t n, int64_t i, uint64_t hi[2], uint32_t lo[2], bool ok[2]) {
   double2 rv = make_double2(0.0, 0.0);
   int2 ov = make_int2(-1, -1);
   if (2 * i + 1 < n) {
     rv = reinterpret_cast<const double2 *>(r)[i];
-    ov = reinterpret_cast<const int2 *>(oid)[i];
+    ov = oid ? reinterpret_cast<const int2 *>(oid)[i] : make_int2((int)(2 * i), (int)(2 * i + 1));
   } else if (2 * i < n) {
     rv.x = r[2 * i];
-    ov.x = oid[2 * i];
+    ov.x = oid ? oid[2 * i] : (int)(2 * i);
   }
   hi[0] = topk_rank_key((uint64_t)__double_as_longlong(rv.x));
   hi[1] = topk_rank_key((uint64_t)__double_as_longlong(rv.y));
@@ -211,18 +211,27 @@ __global__ __launch_bounds__(kTopkThreads) void k_topk_collect(const double *__r
   stage_flush(st, okey, olo, counter, cap);
 }
 
-int topk_state(pr_graph *g, TopkState **out) {
-  if (!g->topk) {
+// The select's scratch (histograms, launch geometry), allocated on first use.
+int topk_scratch(TopkState **st, int device) {
+  if (!*st) {
     TopkState *t = new (std::nothrow) TopkState();
     if (!t) return fail(PR_ERR_OOM, "host allocation failed");
-    g->topk = t;
+    *st = t;
   }
-  TopkState *t = g->topk;
-  if (!t->oid.p) {
+  TopkState *t = *st;
+  if (!t->hist.p) {
     int cus = 0;
-    PR_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, g->device));
+    PR_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
     t->grid_max = std::max(1, cus) * kTopkBlocksPerCU;
     PR_TRY(t->hist.alloc(sizeof(uint32_t) * (kTopkHistWords + 2)));
+  }
+  return PR_OK;
+}
+
+int topk_state(pr_graph *g, TopkState **out) {
+  PR_TRY(topk_scratch(&g->topk, g->device));
+  TopkState *t = g->topk;
+  if (!t->oid.p) {
     DevBuf oid;
     PR_TRY(oid.alloc(sizeof(int32_t) * (size_t)std::max<int64_t>(g->n_rows, 1)));
     if (g->n_rows > 0)
@@ -245,42 +254,58 @@ unsigned topk_grid(const TopkState *t, int64_t n) {
 
 }  // namespace
 
-size_t topk_bytes(const pr_graph *g) {
-  const TopkState *t = g->topk;
+size_t topk_state_bytes(const TopkState *t) {
   if (!t) return 0;
   return t->oid.bytes + t->hist.bytes + t->ckey.bytes + t->cid.bytes + t->out_id.bytes + t->out_rank.bytes;
 }
 
+void topk_state_free(TopkState *t) { delete t; }  // DevBufs free their memory
+
+size_t topk_bytes(const pr_graph *g) { return topk_state_bytes(g->topk); }
+
 void topk_destroy(pr_graph *g) {
-  delete g->topk;  // DevBufs free their memory
+  topk_state_free(g->topk);
   g->topk = nullptr;
 }
 
 int topk_part(pr_graph *g, int64_t k, int64_t narrow_div, int32_t *ids_out, double *ranks_out, int32_t *n_out,
               int32_t *info) {
   PR_TRY(join_exchange(g));
-  hipStream_t s = g->stream;
-  PR_HIP(hipStreamSynchronize(s));
-  const int64_t n = std::min<int64_t>(k, g->n_local);
-  int passes = 0, passes_cand = 0, narrowed_at = -1;
-  if (n > 0) {
+  PR_HIP(hipStreamSynchronize(g->stream));
+  if (std::min<int64_t>(k, g->n_local) > 0) {
     if (g->n_rows >= (int64_t(1) << 32)) return fail(PR_ERR_INVALID, "pr_get_topk: n_rows >= 2^32");
     TopkState *t = nullptr;
-    PR_TRY(topk_state(g, &t));
+    PR_TRY(topk_state(g, &t));  // uploads the row -> original ID map on the first call
+  }
+  return topk_select(&g->topk, g->device, g->stream, g->r.as<double>(), g->topk ? g->topk->oid.as<int32_t>() : nullptr,
+                     g->n_rows, g->n_local, k, narrow_div, ids_out, ranks_out, n_out, info);
+}
+
+// The select over n_rows (rank, original ID) rows of which n_owned are not holes; oid == nullptr:
+// row i is vertex i (no holes).  *state is created on first use.
+
+int topk_select(TopkState **state, int device, hipStream_t s, const double *r, const int32_t *oid, int64_t n_rows,
+                int64_t n_owned, int64_t k, int64_t narrow_div, int32_t *ids_out, double *ranks_out, int32_t *n_out,
+                int32_t *info) {
+  PR_HIP(hipStreamSynchronize(s));
+  const int64_t n = std::min<int64_t>(k, n_owned);
+  int passes = 0, passes_cand = 0, narrowed_at = -1;
+  if (n > 0) {
+    if (!oid && n_rows >= (int64_t(1) << 31)) return fail(PR_ERR_INVALID, "top-K: n_rows >= 2^31");
+    PR_TRY(topk_scratch(state, device));
+    TopkState *t = *state;
     if (t->out_cap < n) {
       t->out_cap = 0;
       PR_TRY(t->out_id.alloc(sizeof(int32_t) * (size_t)n));
       PR_TRY(t->out_rank.alloc(sizeof(uint64_t) * (size_t)n));
       t->out_cap = n;
     }
-    const double *r = g->r.as<double>();
-    const int32_t *oid = t->oid.as<int32_t>();
     uint32_t *hist = t->hist.as<uint32_t>();
     uint32_t *ctr = hist + kTopkHistWords;
     PR_HIP(hipMemsetAsync(hist, 0, sizeof(uint32_t) * (kTopkHistWords + 2), s));
     uint64_t thi = 0;
     uint32_t tlo = 0;
-    if (n < g->n_local) {  // otherwise every owned row is selected: threshold 0
+    if (n < n_owned) {  // otherwise every owned row is selected: threshold 0
       int64_t cand_n = 0;
       auto hist_pass = [&](int p, uint64_t phi, uint32_t plo, uint32_t *h) -> int {
         uint32_t *dh = hist + (size_t)p * kTopkBins;
@@ -289,8 +314,8 @@ int topk_part(pr_graph *g, int64_t k, int64_t narrow_div, int32_t *ids_out, doub
                              nullptr, t->ckey.as<uint64_t>(), t->cid.as<uint32_t>(), cand_n, p, phi, plo, dh);
           ++passes_cand;
         } else {
-          hipLaunchKernelGGL(k_topk_hist<false>, dim3(topk_grid(t, g->n_rows)), dim3(kTopkThreads), 0, s, r, oid,
-                             nullptr, nullptr, g->n_rows, p, phi, plo, dh);
+          hipLaunchKernelGGL(k_topk_hist<false>, dim3(topk_grid(t, n_rows)), dim3(kTopkThreads), 0, s, r, oid,
+                             nullptr, nullptr, n_rows, p, phi, plo, dh);
         }
         PR_HIP(hipGetLastError());
         PR_HIP(hipMemcpyAsync(h, dh, sizeof(uint32_t) * kTopkBins, hipMemcpyDeviceToHost, s));
@@ -299,15 +324,15 @@ int topk_part(pr_graph *g, int64_t k, int64_t narrow_div, int32_t *ids_out, doub
       };
       auto after_pass = [&](int p, uint64_t phi, uint32_t plo, uint64_t count) -> int {
         if (narrowed_at >= 0 || narrow_div <= 0 || p >= kTopkDigits) return PR_OK;
-        if ((int64_t)count > g->n_rows / narrow_div) return PR_OK;
+        if ((int64_t)count > n_rows / narrow_div) return PR_OK;
         if (t->cand_cap < (int64_t)count) {
           t->cand_cap = 0;
           PR_TRY(t->ckey.alloc(sizeof(uint64_t) * (size_t)count));
           PR_TRY(t->cid.alloc(sizeof(uint32_t) * (size_t)count));
           t->cand_cap = (int64_t)count;
         }
-        hipLaunchKernelGGL(k_topk_collect<false>, dim3(topk_grid(t, g->n_rows)), dim3(kTopkThreads), 0, s, r, oid,
-                           g->n_rows, p, phi, plo, t->ckey.as<uint64_t>(), t->cid.as<uint32_t>(), ctr, (uint32_t)count);
+        hipLaunchKernelGGL(k_topk_collect<false>, dim3(topk_grid(t, n_rows)), dim3(kTopkThreads), 0, s, r, oid,
+                           n_rows, p, phi, plo, t->ckey.as<uint64_t>(), t->cid.as<uint32_t>(), ctr, (uint32_t)count);
         PR_HIP(hipGetLastError());
         cand_n = (int64_t)count;
         narrowed_at = p;
@@ -315,8 +340,8 @@ int topk_part(pr_graph *g, int64_t k, int64_t narrow_div, int32_t *ids_out, doub
       };
       PR_TRY(topk_select_threshold((uint64_t)n, hist_pass, after_pass, &thi, &tlo, &passes));
     }
-    hipLaunchKernelGGL(k_topk_collect<true>, dim3(topk_grid(t, g->n_rows)), dim3(kTopkThreads), 0, s, r, oid,
-                       g->n_rows, 0, thi, tlo, t->out_rank.as<uint64_t>(), t->out_id.as<uint32_t>(), ctr + 1, (uint32_t)n);
+    hipLaunchKernelGGL(k_topk_collect<true>, dim3(topk_grid(t, n_rows)), dim3(kTopkThreads), 0, s, r, oid,
+                       n_rows, 0, thi, tlo, t->out_rank.as<uint64_t>(), t->out_id.as<uint32_t>(), ctr + 1, (uint32_t)n);
     PR_HIP(hipGetLastError());
     uint32_t counts[2] = {0, 0};
     std::vector<uint32_t> hid((size_t)n);

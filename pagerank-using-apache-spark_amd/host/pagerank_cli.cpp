@@ -3,6 +3,7 @@
 //   pagerank <input-path> [iterations=10] [--format=edges|ccjson] [--out DIR]
 //            [--save-every-iter] [--dangling=local|none] [--device N] [--quiet] [--stats]
 //            [--resume DIR/PageRank<i>] [--devices D0,D1,...] [--top K] [--seeds FILE]
+//            [--seed-set FILE]...
 //
 // Input (libpagerank_host): "src dst" edge list ("src" alone = record without links), or
 // --format=ccjson "url<TAB>json" Common Crawl metadata records (Sparky.java:61-123).  URLs are
@@ -28,6 +29,13 @@
 // and checked before the graph is created: a bad one exits with status 2 without touching a GPU.
 // Combines with every other option; outputs have the same form as without it.
 //   pagerank edges.txt 20 --seeds seeds.txt --top 100
+// --seed-set FILE (1 to 16 times): batched personalised PageRank.  Every FILE is a seed file as for
+// --seeds and gives one personalised ranking; all of them run as one batch (pr_batch_*), one pass
+// over the graph per iteration for all sets.  Per set, in command-line order, the listing is a line
+// "# seed set <j>: <FILE>" followed by that set's "<url> has rank: <r>." lines (with --top K its K
+// best, pr_batch_get_topk); --out DIR writes DIR/seedset<j>/PageRank<last>/part-00000 + _SUCCESS.
+// Not with --seeds, --devices, --resume or --save-every-iter (usage errors, before any GPU work).
+//   pagerank edges.txt 20 --seed-set alice.txt --seed-set bob.txt --top 100
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -48,6 +56,7 @@ struct Options {
   int device = 0;
   int top = 0;  // --top K (0: list every URL)
   std::vector<int> devices;  // --devices: one part per entry (empty: one part on `device`)
+  std::vector<std::string> seed_sets;  // --seed-set, in command-line order (empty: no batch)
 };
 
 std::vector<int> parse_devices(const std::string &s) {
@@ -69,7 +78,9 @@ std::vector<int> parse_devices(const std::string &s) {
   std::fprintf(stderr,
                "usage: pagerank <input-path> [iterations=10] [--format=edges|ccjson] [--out DIR]\n"
                "                [--save-every-iter] [--dangling=local|none] [--device N] [--quiet] [--stats]\n"
-               "                [--resume DIR/PageRank<i>] [--devices D0,D1,...] [--top K] [--seeds FILE]\n");
+               "                [--resume DIR/PageRank<i>] [--devices D0,D1,...] [--top K] [--seeds FILE]\n"
+               "                [--seed-set FILE]...  (1 to 16 seed files, run as one batch; not with --seeds,\n"
+               "                --devices, --resume or --save-every-iter)\n");
   std::exit(2);
 }
 
@@ -92,6 +103,8 @@ Options parse(int argc, char **argv) {
     else if (a.rfind("--resume=", 0) == 0) o.resume = a.substr(9);
     else if (a == "--seeds" && i + 1 < argc) o.seeds = argv[++i];
     else if (a.rfind("--seeds=", 0) == 0) o.seeds = a.substr(8);
+    else if (a == "--seed-set" && i + 1 < argc) o.seed_sets.push_back(argv[++i]);
+    else if (a.rfind("--seed-set=", 0) == 0) o.seed_sets.push_back(a.substr(11));
     else if ((a == "--devices" && i + 1 < argc) || a.rfind("--devices=", 0) == 0) {
       o.devices = parse_devices(a == "--devices" ? std::string(argv[++i]) : a.substr(10));
       if (o.devices.empty()) usage("--devices takes a comma-separated list of device numbers");
@@ -110,6 +123,12 @@ Options parse(int argc, char **argv) {
   }
   if (o.path.empty()) usage("missing input path");
   if (o.iterations < 0) usage("iterations must be >= 0");
+  if (!o.seed_sets.empty()) {
+    if (!o.seeds.empty()) usage("--seeds and --seed-set are exclusive");
+    if (o.seed_sets.size() > 16) usage("--seed-set: at most 16 seed sets");
+    if (!o.devices.empty() || !o.resume.empty() || o.save_every)
+      usage("--seed-set does not combine with --devices, --resume or --save-every-iter");
+  }
   return o;
 }
 
@@ -195,6 +214,61 @@ int run_group(const Options &o, const prh_edges *edges, const Seeds &seeds, cons
   return rc;
 }
 
+// --seed-set: every set is one column of a batch over one graph (which keeps its canonical CSR: the
+// batch runs over it).  Prints the iteration lines, then per set its header and listing.
+int run_seed_sets(const Options &o, const prh_edges *edges, const std::vector<Seeds> &sets) {
+  const int32_t V = prh_n_vertices(edges);
+  pr_graph *g = nullptr;
+  pr_batch *b = nullptr;
+  int rc = pr_graph_create(o.device, V, prh_n_edges(edges), prh_src(edges), prh_dst(edges), o.flags, &g);
+  if (rc == PR_OK) rc = pr_batch_create(g, (int32_t)sets.size(), &b);
+  for (size_t j = 0; j < sets.size() && rc == PR_OK; ++j)
+    rc = pr_batch_set_teleport_sparse(b, (int32_t)j, sets[j].n, sets[j].ids, sets[j].values.data(), 0.0);
+  if (rc == PR_OK) rc = pr_batch_reset(b, 0.15, 0.85, nullptr);
+  for (int it = 0; it < o.iterations && rc == PR_OK; ++it) {
+    std::printf("Starting iter%d\n", it);
+    rc = pr_batch_step(b, 1);
+  }
+  int error = 0;
+  std::vector<double> ranks((size_t)V + 1);
+  const int32_t top_k = o.top < V ? o.top : V;
+  std::vector<int32_t> top_ids((size_t)top_k + 1);
+  std::vector<double> top_ranks((size_t)top_k + 1);
+  for (size_t j = 0; j < sets.size() && rc == PR_OK; ++j) {
+    const bool full = !o.out.empty() || (o.top == 0 && !o.quiet);
+    if (full) rc = pr_batch_get_ranks(b, (int32_t)j, ranks.data());
+    if (rc == PR_OK && !o.out.empty() && o.iterations > 0 &&
+        prh_write_part(edges, (o.out + "/seedset" + std::to_string(j)).c_str(), o.iterations - 1, ranks.data()) != 0) {
+      std::fprintf(stderr, "pagerank: %s\n", prh_last_error());
+      error = 1;
+    }
+    if (rc != PR_OK || o.quiet) continue;
+    std::printf("# seed set %zu: %s\n", j, o.seed_sets[j].c_str());
+    std::fflush(stdout);
+    int rc_out = 0;
+    if (o.top > 0) {
+      int32_t n = 0;
+      rc = pr_batch_get_topk(b, (int32_t)j, top_k, top_ids.data(), top_ranks.data(), &n);
+      if (rc == PR_OK) rc_out = prh_write_has_rank_ids(edges, nullptr, top_ids.data(), top_ranks.data(), n);
+    } else {
+      rc_out = prh_write_has_rank(edges, nullptr, ranks.data());
+    }
+    if (rc_out != 0) {
+      std::fprintf(stderr, "pagerank: %s\n", prh_last_error());
+      error = 1;
+    }
+    std::fflush(stdout);
+  }
+  const std::string err = rc == PR_OK ? std::string() : std::string(pr_last_error());
+  pr_batch_destroy(b);  // before the graph it borrows
+  pr_graph_destroy(g);
+  if (rc != PR_OK) {
+    std::fprintf(stderr, "pagerank: --seed-set run failed (%d): %s\n", rc, err.c_str());
+    return 1;
+  }
+  return error;
+}
+
 }  // namespace
 
 using Clock = std::chrono::steady_clock;
@@ -220,6 +294,25 @@ int main(int argc, char **argv) {
     seeds.values.resize((size_t)seeds.n);
     prh_seed_teleport(seeds.n, weights, 0.15, V, seeds.values.data());
     prh_free_seeds(nullptr, weights);
+  }
+  if (!o.seed_sets.empty()) {  // every file read and checked before any graph exists
+    std::vector<Seeds> sets(o.seed_sets.size());
+    int rc = 0;
+    for (size_t j = 0; j < sets.size() && rc == 0; ++j) {
+      double *weights = nullptr;
+      if (prh_read_seeds(edges, o.seed_sets[j].c_str(), &sets[j].n, &sets[j].ids, &weights) != 0) {
+        std::fprintf(stderr, "pagerank: --seed-set %s: %s\n", o.seed_sets[j].c_str(), prh_last_error());
+        rc = 2;
+        break;
+      }
+      sets[j].values.resize((size_t)sets[j].n);
+      prh_seed_teleport(sets[j].n, weights, 0.15, V, sets[j].values.data());
+      prh_free_seeds(nullptr, weights);
+    }
+    if (rc == 0) rc = run_seed_sets(o, edges, sets);
+    for (Seeds &s : sets) prh_free_seeds(s.ids, nullptr);
+    prh_free(edges);
+    return rc;
   }
   const double ms_read = ms_since(t_job);  // parse + first-appearance interning (host)
   double ms_build = 0.0, ms_run = 0.0;

@@ -60,7 +60,13 @@ EXPORTED = [
     "pr_graph_destroy", "pr_gen_rmat", "pr_gen_er", "pr_gen_chunglu", "pr_intern_device", "pr_group_reset",
     "pr_group_step", "pr_group_sync", "pr_get_topk", "pr_group_topk", "pr_topk_merge",
     "pr_set_teleport", "pr_set_teleport_sparse",
+    "pr_batch_create", "pr_batch_set_teleport", "pr_batch_set_teleport_sparse", "pr_batch_reset", "pr_batch_step",
+    "pr_batch_sync", "pr_batch_get_ranks", "pr_batch_get_norms", "pr_batch_get_topk", "pr_batch_info",
+    "pr_batch_destroy",
 ]
+# pr_batch_info, in order
+BATCH_INFO_NAMES = ["width", "stride", "n_units", "n_long_rows", "device_bytes", "iters", "last_step_ns"]
+BATCH_MAX_WIDTH = 16
 
 ITER_CB = ctypes.CFUNCTYPE(None, ctypes.c_int32, ctypes.POINTER(ctypes.c_double), ctypes.c_double,
                            ctypes.c_double, ctypes.c_double, ctypes.c_void_p)
@@ -130,6 +136,17 @@ def load() -> ctypes.CDLL:
         "pr_topk_merge": ([i32, P, P, P, i32, P, P, P], ctypes.c_int),
         "pr_set_teleport": ([P, P], ctypes.c_int),
         "pr_set_teleport_sparse": ([P, i32, P, P, dbl], ctypes.c_int),
+        "pr_batch_create": ([P, i32, P], ctypes.c_int),
+        "pr_batch_set_teleport": ([P, i32, P], ctypes.c_int),
+        "pr_batch_set_teleport_sparse": ([P, i32, i32, P, P, dbl], ctypes.c_int),
+        "pr_batch_reset": ([P, dbl, dbl, P], ctypes.c_int),
+        "pr_batch_step": ([P, i32], ctypes.c_int),
+        "pr_batch_sync": ([P], ctypes.c_int),
+        "pr_batch_get_ranks": ([P, i32, P], ctypes.c_int),
+        "pr_batch_get_norms": ([P, P, P], ctypes.c_int),
+        "pr_batch_get_topk": ([P, i32, i32, P, P, P], ctypes.c_int),
+        "pr_batch_info": ([P, P, i32], ctypes.c_int),
+        "pr_batch_destroy": ([P], None),
         # internal (not in the header): pr_get_topk with the narrowing threshold and the pass counts
         "pr_topk_select_ex": ([P, i32, i64, P, P, P, P], ctypes.c_int),
     }

@@ -1,0 +1,97 @@
+"""Batched personalised PageRank on top of libpagerank_hip's pr_batch_* (include/pagerank_hip.h).
+
+``PageRankBatch(graph, width)`` advances up to 16 rank vectors over one ``PageRankGraph`` together:
+one pass streams the graph's column indices once for all of them.  Every column has its own
+teleport vector (``set_teleport`` / ``set_teleport_sparse``; a column without one uses the scalar
+of ``reset``) and runs exactly the iteration ``PageRankGraph.set_teleport`` documents.  The graph
+must be a single part that kept its canonical CSR; the batch borrows it, so close the batch first
+(the context manager does).
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+
+from . import _lib
+from ._lib import check
+from .graph import PageRankGraph, _init_array, _ptr, _sparse_arrays, _teleport_array
+
+
+class PageRankBatch:
+    """One ``pr_batch`` handle: ``width`` personalised runs over ``graph``, stepped together."""
+
+    def __init__(self, graph: PageRankGraph, width: int):
+        self._h = ctypes.c_void_p()
+        self._graph = graph  # keeps the borrowed graph alive
+        self.n_vertices = graph.n_vertices
+        self.width = int(width)
+        check(_lib.load().pr_batch_create(graph._h, self.width, ctypes.byref(self._h)))
+
+    # -- lifecycle ---------------------------------------------------------------------------
+    def close(self) -> None:
+        if getattr(self, "_h", None) and self._h.value:
+            _lib.load().pr_batch_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    # -- teleport vectors --------------------------------------------------------------------
+    def set_teleport(self, column: int, teleport) -> None:
+        """pr_batch_set_teleport: float64[V] in original-ID order (the teleport *term* of every
+        vertex), or None: the column is back to the scalar of reset().  Survives reset()."""
+        t = _teleport_array(teleport, self.n_vertices)
+        check(_lib.load().pr_batch_set_teleport(self._h, int(column), _ptr(t)))
+
+    def set_teleport_sparse(self, column: int, ids, values, rest: float = 0.0) -> None:
+        """pr_batch_set_teleport_sparse: t[ids[i]] = values[i], every other vertex ``rest``."""
+        i, v = _sparse_arrays(ids, values)
+        check(_lib.load().pr_batch_set_teleport_sparse(self._h, int(column), int(i.shape[0]), _ptr(i), _ptr(v),
+                                                       float(rest)))
+
+    # -- iteration ---------------------------------------------------------------------------
+    def reset(self, *, teleport: float = 0.15, damping: float = 0.85, init_ranks=None) -> None:
+        init = _init_array(init_ranks, self.n_vertices)
+        check(_lib.load().pr_batch_reset(self._h, teleport, damping, _ptr(init)))
+
+    def step(self, iterations: int) -> None:
+        check(_lib.load().pr_batch_step(self._h, int(iterations)))
+
+    def sync(self) -> None:
+        check(_lib.load().pr_batch_sync(self._h))
+
+    # -- results -----------------------------------------------------------------------------
+    def ranks(self, column: int) -> np.ndarray:
+        out = np.zeros(max(self.n_vertices, 1), np.float64)
+        check(_lib.load().pr_batch_get_ranks(self._h, int(column), _ptr(out)))
+        return out[: self.n_vertices]
+
+    def norms(self):
+        """(dc, l1): float64[width] each -- per column the dangling sum the last iteration used and
+        the L1 distance it moved the ranks."""
+        dc, l1 = np.zeros(self.width, np.float64), np.zeros(self.width, np.float64)
+        check(_lib.load().pr_batch_get_norms(self._h, _ptr(dc), _ptr(l1)))
+        return dc, l1
+
+    def topk(self, column: int, k: int):
+        """pr_batch_get_topk: PageRankGraph.topk over one column; (ids int32[n], ranks float64[n])."""
+        k = int(k)
+        ids, rk = np.zeros(max(k, 1), np.int32), np.zeros(max(k, 1), np.float64)
+        n = ctypes.c_int32(0)
+        check(_lib.load().pr_batch_get_topk(self._h, int(column), k, _ptr(ids), _ptr(rk), ctypes.byref(n)))
+        return ids[: n.value], rk[: n.value]
+
+    def info(self) -> dict:
+        a = np.zeros(len(_lib.BATCH_INFO_NAMES), np.int64)
+        check(_lib.load().pr_batch_info(self._h, _ptr(a), len(a)))
+        return dict(zip(_lib.BATCH_INFO_NAMES, (int(x) for x in a)))

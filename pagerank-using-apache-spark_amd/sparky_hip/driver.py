@@ -2,7 +2,7 @@
 
 CLI: ``python -m sparky_hip <input-path> [iterations=10] [--format edges|ccjson]
 [--out DIR] [--save-every-iter] [--dangling=local|none] [--device N] [--quiet]
-[--resume DIR/PageRank<i>] [--devices D0,D1,...] [--top K] [--seeds FILE]``
+[--resume DIR/PageRank<i>] [--devices D0,D1,...] [--top K] [--seeds FILE] [--seed-set FILE]...``
 
 * input: text edge list, ``src dst`` per line; a single-token line ``src`` is a record without
   ``a`` links (Sparky.java:114-118).  Tokens (URLs) are taken verbatim and interned to dense
@@ -25,6 +25,14 @@ CLI: ``python -m sparky_hip <input-path> [iterations=10] [--form
   ``set_teleport_sparse``); the dangling term stays uniform.  The file is read and checked before
   the graph is created: a bad one exits with status 2 without touching a GPU.  Same outputs as the
   C++ CLI: ``pagerank edges.txt 20 --seeds seeds.txt --top 100``.
+* ``--seed-set FILE`` (1 to 16 times): batched personalised PageRank.  Every FILE is a seed file as
+  for ``--seeds`` and gives one personalised ranking; all of them run as one batch
+  (``PageRankBatch``), one pass over the graph per iteration for all sets.  Per set, in
+  command-line order, the listing is a line ``# seed set <j>: <FILE>`` followed by that set's
+  ``<url> has rank: <r>.`` lines (with ``--top K`` its K best); ``--out DIR`` writes
+  ``DIR/seedset<j>/PageRank<last>/part-00000`` + ``_SUCCESS``.  Not with ``--seeds``,
+  ``--devices``, ``--resume`` or ``--save-every-iter`` (usage errors, before any GPU work).  Same
+  bytes as the C++ CLI.
 """
 from __future__ import annotations
 
@@ -166,6 +174,33 @@ def _run_group(edges, devices, dangling, n_run, init, cb, want_ranks, top=0, see
             g.close()
 
 
+def _run_seed_sets(edges, a, sets, top, out) -> None:
+    """--seed-set: every set is one column of a batch over one graph (which keeps its canonical
+    CSR: the batch runs over it).  The iteration lines, then per set its header and listing."""
+    from .batch import PageRankBatch
+
+    with PageRankGraph(edges.n_vertices, edges.src, edges.dst, device=a.device, dangling=a.dangling) as g:
+        with PageRankBatch(g, len(sets)) as b:
+            for j, (ids, values) in enumerate(sets):
+                b.set_teleport_sparse(j, ids, values)
+            b.reset()
+            for it in range(a.iterations):
+                out.write(f"Starting iter{it}\n")
+                b.step(1)
+            for j in range(len(sets)):
+                ranks = b.ranks(j) if a.out or (not top and not a.quiet) else None
+                if a.out and a.iterations > 0:
+                    edges.write_part(os.path.join(a.out, f"seedset{j}"), a.iterations - 1, ranks)
+                if a.quiet:
+                    continue
+                out.write(f"# seed set {j}: {a.seed_set[j]}\n")
+                out.flush()
+                if top:
+                    edges.write_has_rank_ids(None, *b.topk(j, top))
+                else:
+                    edges.write_has_rank(None, ranks)
+
+
 def main(argv=None) -> int:
     from ._host import HostEdges, HostError, seed_teleport
 
@@ -185,10 +220,20 @@ def main(argv=None) -> int:
                     help="list only the K highest-ranked URLs (selected on the GPU)")
     ap.add_argument("--seeds", default=None, metavar="FILE",
                     help="personalised PageRank: seed URLs, one 'url' or 'url weight' per line")
+    ap.add_argument("--seed-set", action="append", default=None, metavar="FILE",
+                    help="batched personalised PageRank: 1 to 16 seed files, run as one batch; not with --seeds, "
+                         "--devices, --resume or --save-every-iter")
     a = ap.parse_args(argv)
     if a.top is not None and a.top < 1:
         ap.error("--top takes a count K >= 1")
     top = a.top or 0
+    if a.seed_set:
+        if a.seeds is not None:
+            ap.error("--seeds and --seed-set are exclusive")
+        if len(a.seed_set) > 16:
+            ap.error("--seed-set: at most 16 seed sets")
+        if a.devices is not None or a.resume or a.save_every_iter:
+            ap.error("--seed-set does not combine with --devices, --resume or --save-every-iter")
     devices = [a.device]
     if a.devices is not None:
         try:
@@ -206,6 +251,20 @@ def main(argv=None) -> int:
             return 2
         seeds = (ids, seed_teleport(weights, edges.n_vertices))  # the native expression: the C++ CLI's bits
     out = sys.stdout
+    if a.seed_set:  # every file read and checked before any graph exists
+        sets = []
+        for path in a.seed_set:
+            try:
+                ids, weights = edges.read_seeds(path)
+            except HostError as e:
+                sys.stderr.write(f"sparky_hip: --seed-set {path}: {e}\n")
+                edges.close()
+                return 2
+            sets.append((ids, seed_teleport(weights, edges.n_vertices)))
+        _run_seed_sets(edges, a, sets, top, out)
+        out.flush()
+        edges.close()
+        return 0
     init, start = None, 0
     if a.resume:
         init = edges.read_ranks(a.resume)

@@ -76,7 +76,8 @@ extern "C" {
 #define PR_INFO_LAYOUT 21      /* 0 fused, 1 split (column classes + partial slots)          */
 #define PR_INFO_HOT_COVER 22   /* in-links read from the LDS hot sets, parts per million      */
 #define PR_INFO_CODE_BITS 23   /* bits per in-link of the split layout's entry codes: 20 / 24 compact, 32 */
-#define PR_INFO_COUNT 24
+#define PR_INFO_HOT_GATHER 24  /* cold gathers of the next k_spmv_hot launch: 0 per position, 1 dense (PR_OPT_HOT_GATHER); 0 fused */
+#define PR_INFO_COUNT 25
 
 /* ---- pr_get_stats indices ------------------------------------------------------------- */
 #define PR_STAT_ITERS 0          /* iterations run since the last reset                     */
@@ -246,6 +247,13 @@ int pr_get_stats(pr_graph *g, double *stats, int32_t n_stats);
  * 1 = the runtime's blit kernel on the CUs (link speed; it competes with the SpMV for CUs).  Local
  * to the rank (not collective); no effect on results. */
 #define PR_OPT_XCHG_IPC_BLIT 4
+/* PR_OPT_HOT_GATHER (test hook): how k_spmv_hot gathers a unit's cold entries: -1 = auto (the default:
+ * dense gathers once a pass has enough wave units per CU, per-position gathers below), 0 = one gather
+ * per entry position, 1 = dense gathers.  Both give the same bits; the option lets a small graph run
+ * the path the size rule keeps for large ones.  Any other value: PR_ERR_INVALID.  Accepted without
+ * effect on a handle of the fused layout (PR_INFO_CLASSES == 1).  PR_INFO_HOT_GATHER reports the path
+ * the next launch takes. */
+#define PR_OPT_HOT_GATHER 5
 int pr_set_option(pr_graph *g, int32_t option, int64_t value);
 
 /* Multi-process (one process per GPU): rank 0 creates an id, the host ships the 128 bytes

@@ -234,7 +234,8 @@ int pr_graph_info(const pr_graph *g, int64_t *info, int32_t n_info) {
                                     xchg_volume(g, true), xchg_volume(g, false), g->n_slots,
                                     g->C > 1 ? (int64_t)g->hot.P * g->hot.Kp : 0,
                                     g->C == 1 ? 0 : 3, g->gather_est, g->n_walk_groups, g->layout,
-                                    g->hot_cover_ppm, g->C > 1 ? (g->code == pr::kCodeC20 || g->code == pr::kCodeC20P ? 20 : g->code == pr::kCodeC24 || g->code == pr::kCodeC24P ? 24 : 32) : 0};
+                                    g->hot_cover_ppm, g->C > 1 ? (g->code == pr::kCodeC20 || g->code == pr::kCodeC20P ? 20 : g->code == pr::kCodeC24 || g->code == pr::kCodeC24P ? 24 : 32) : 0,
+                                    pr::hot_gather_dense(g) ? 1 : 0};
   for (int32_t i = 0; i < n_info && i < PR_INFO_COUNT; ++i) info[i] = v[i];
   return PR_OK;
 }
@@ -333,6 +334,11 @@ int pr_set_option(pr_graph *g, int32_t option, int64_t value) {
   if (option == PR_OPT_HOT_RESERVE) {
     if (value < 0 || value > 3) return fail(PR_ERR_INVALID, "PR_OPT_HOT_RESERVE: 0..3 CUs per XCD");
     if (g->C > 1) PR_TRY(pr::set_hot_reserve(g, (int)value));
+    return PR_OK;
+  }
+  if (option == PR_OPT_HOT_GATHER) {
+    if (value < -1 || value > 1) return fail(PR_ERR_INVALID, "PR_OPT_HOT_GATHER: -1 (auto), 0 (per position) or 1 (dense)");
+    if (g->C > 1) g->hot_gather = (int)value;
     return PR_OK;
   }
   if (option == PR_OPT_XCHG_IPC_BLIT) {

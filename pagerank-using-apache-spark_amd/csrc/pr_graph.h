@@ -98,6 +98,7 @@ struct pr_graph {
   pr::HotGeom hot{};
   int hot_grid = 0;       // workgroups of k_spmv_hot (a multiple of C: one per CU)
   int hot_grid_full = 0;  // the same without reserved CUs (PR_OPT_HOT_RESERVE)
+  int hot_gather = -1;    // PR_OPT_HOT_GATHER: -1 the size rule, 0 per-position, 1 dense cold gathers
   // per-row walk in k_epilogue_grp (PR_BOPT_EPI_WALK): per group the first of its u16 slot
   // positions in epos, or -1 for the class loop (eoff, i64)
   bool epi_walk = false;
@@ -240,6 +241,9 @@ int n_hot_phases(const pr_graph *g);
 // k_spmv_hot leaves `per_xcd` CUs of every XCD free (phased schedule only: its grid need only be
 // a multiple of the XCD count)
 int set_hot_reserve(pr_graph *g, int per_xcd);
+// the cold gathers of the next k_spmv_hot launch: dense (true) or one per entry position
+// (PR_OPT_HOT_GATHER, or the size rule); false without column classes
+bool hot_gather_dense(const pr_graph *g);
 int iter_step(pr_graph *g, int32_t iterations);
 int iter_compute(pr_graph *g);  // one iteration without the exchange; flips g->cur
 // timing (every part's g->timing): per receiving part one xchg_ev interval, its copies on xstream

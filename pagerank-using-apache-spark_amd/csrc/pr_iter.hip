@@ -332,7 +332,13 @@ int set_hot_reserve(pr_graph *g, int per_xcd) {
 // (8.8 K per CU) -2.5 %, ER s24 (2 K) -0.5 %; below it a unit's latency chain matters more than its
 // gather instructions (R-MAT s20, 0.12 K: +11 %; LiveJournal shape, 0.5 K: +0.7 %; with the rounds of
 // 256 still +15 % / +0.4 %, profiles/r06/dense/r6_dense0/).
+// PR_OPT_HOT_GATHER (a test hook) forces either path whatever the size; the grid plays no part then.
 constexpr int64_t kDenseUnitsPerCU = 1024;
+bool hot_gather_dense(const pr_graph *g) {
+  if (g->C <= 1) return false;
+  if (g->hot_gather >= 0) return g->hot_gather == 1;
+  return g->n_hunits >= kDenseUnitsPerCU * (int64_t)g->hot_grid_full;
+}
 template <bool DENSE>
 void *hot_kernel(int code) {
   return code == kCodeC20    ? reinterpret_cast<void *>(k_spmv_hot<kCodeC20, DENSE>)
@@ -345,7 +351,7 @@ void *hot_kernel(int code) {
 int launch_hot(pr_graph *g, int in, int ph0, int ph1) {
   if (ph1 < 0) ph1 = n_hot_phases(g);
   const CodeSrc cd{g->colh.p, g->cside.as<uint32_t>()};
-  const bool dense = g->n_hunits >= kDenseUnitsPerCU * (int64_t)g->hot_grid_full;
+  const bool dense = hot_gather_dense(g);
   auto kern = reinterpret_cast<decltype(&k_spmv_hot<kCodeU32, false>)>(dense ? hot_kernel<true>(g->code)
                                                                               : hot_kernel<false>(g->code));
   if (g->hot.lds_bytes() > (size_t)kHotLdsBytes) return fail(PR_ERR_STATE, "hot set exceeds the LDS");

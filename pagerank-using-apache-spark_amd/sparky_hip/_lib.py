@@ -37,7 +37,7 @@ PR_VF_KEY, PR_VF_SINK, PR_VF_NOLINK, PR_VF_INDEG0 = 1, 2, 4, 8
 INFO_NAMES = ["n_vertices", "n_edges", "n_sink", "n_nolink", "n_indeg0", "max_indeg", "local_rows",
               "local_edges", "part", "n_parts", "n_units", "n_long_rows", "device_bytes", "classes",
               "xchg_send", "xchg_recv", "partial_slots", "hot_slots", "epilogue", "gather_est",
-              "walk_groups", "layout", "hot_cover_ppm", "code_bits"]
+              "walk_groups", "layout", "hot_cover_ppm", "code_bits", "hot_gather"]
 # build options of pr_graph_create_ex (PR_BOPT_*), by the keyword PageRankGraph(options=...) takes
 BUILD_OPTIONS = {"classes": 1, "hot_slots": 2, "exchange_allgather": 3, "xchg_chunks": 4, "hot_reserve": 5,
                  "epi_walk": 6, "epi_narrow": 7, "codes": 8, "pack_fused": 9, "xchg_sdma": 10,
@@ -49,6 +49,7 @@ PR_OPT_XCHG_CHUNKS = 1
 PR_OPT_HOT_RESERVE = 2
 PR_OPT_XCHG_IPC = 3
 PR_OPT_XCHG_IPC_BLIT = 4
+PR_OPT_HOT_GATHER = 5
 PR_COMM_ID_BYTES = 128
 
 # Every symbol include/pagerank_hip.h declares (checked by tests/test_abi.py).

@@ -271,6 +271,12 @@ class PageRankGraph:
         """pr_set_option(PR_OPT_HOT_RESERVE): CUs per XCD the heavy SpMV kernel leaves free."""
         check(_lib.load().pr_set_option(self._h, _lib.PR_OPT_HOT_RESERVE, int(cus_per_xcd)))
 
+    def set_hot_gather(self, mode: int) -> None:
+        """pr_set_option(PR_OPT_HOT_GATHER), a test hook: the heavy SpMV kernel's cold gathers are one
+        per entry position (0), dense (1), or chosen by the pass's size (-1, the default).  Same bits
+        either way; info()["hot_gather"] reports the path the next launch takes."""
+        check(_lib.load().pr_set_option(self._h, _lib.PR_OPT_HOT_GATHER, int(mode)))
+
     def set_exchange_ipc(self, mode) -> None:
         """pr_set_option(PR_OPT_XCHG_IPC): RCCL path on one node -- every rank pulls the runs it reads
         out of its peers' IPC-mapped send buffers with the copy engines (True / 1) or RCCL send/recv

@@ -59,6 +59,7 @@ def test_headline_config_parity(hip, oracle_c, graph, scale):
         # the product configuration of the bench line
         assert info["layout"] == 1 and info["classes"] == 64 and info["epilogue"] == 3, info
         assert info["hot_slots"] == 18429, info
+        assert info["hot_gather"] == 1, info  # the dense cold gathers (pr_iter.hip kDenseUnitsPerCU)
         if graph != "er":
             assert info["partial_slots"] > (1 << 28), info
         t_build = time.perf_counter()

@@ -38,7 +38,8 @@ def assert_csr_equal(g, csr):
     assert np.array_equal(ex.vflags, csr.vflags)
 
 
-def run_both(hip, oracle_c, V, src, dst, iters, dangling="local", init=None, layout="auto", options=None):
+def run_both(hip, oracle_c, V, src, dst, iters, dangling="local", init=None, layout="auto", options=None,
+             before_close=None):
     csr = oracle_c.build_csr(V, src, dst)
     ref = oracle_c.run(csr, iters, dangling_none=(dangling == "none"), init=init, keep_history=True)
     with hip.PageRankGraph(V, src, dst, dangling=dangling, layout=layout, options=options) as g:
@@ -50,6 +51,8 @@ def run_both(hip, oracle_c, V, src, dst, iters, dangling="local", init=None, lay
         ranks, stats = g.run(iters, init_ranks=init, want_ranks_in_callback=True,
                              callback=lambda it, r, st: hist.append(r))
         info = g.info()
+        if before_close is not None:  # more runs of the same handle
+            before_close(g, ranks)
     return csr, ref, ranks, stats, hist, info
 
 
@@ -642,7 +645,7 @@ def test_compact_codes_bitwise(hip, oracle_c, classes, slots):
         assert g.info()["code_bits"] == 20
 
 
-def _group_ranks(hip, V, src, dst, P, opts, iters):
+def _group_ranks(hip, V, src, dst, P, opts, iters, dense_again=False):
     parts = [hip.PageRankGraph(V, src, dst, part=p, n_parts=P, keep_canonical=False, layout="split",
                                options=opts) for p in range(P)]
     try:
@@ -652,7 +655,17 @@ def _group_ranks(hip, V, src, dst, P, opts, iters):
         grp.step(iters // 2)
         grp.step(iters - iters // 2)
         grp.sync()
-        return grp.ranks(), infos
+        r = grp.ranks()
+        if dense_again:  # the same parts once more with k_spmv_hot's dense cold gathers: the same bits
+            for p in parts:
+                p.set_hot_gather(1)
+                assert p.info()["hot_gather"] == 1
+            grp.reset()
+            grp.step(iters // 2)
+            grp.step(iters - iters // 2)
+            grp.sync()
+            assert np.array_equal(grp.ranks(), r)
+        return r, infos
     finally:
         for p in parts:
             p.close()
@@ -705,15 +718,17 @@ def test_group_exchange_copy_engines(hip, oracle_c, P, chunks):
 def test_piece_codes_widen(hip, oracle_c):
     """A part whose class virtual space passes 2^19 (8 classes over 4.4 M vertices at P = 2:
     own regions of 275 K rows plus ~254 K received sources per class) takes the 3-byte piece codes
-    (kCodeC24P), bitwise the ranks of the 32-bit codes, and matches the oracle."""
+    (kCodeC24P), bitwise the ranks of the 32-bit codes, and matches the oracle.  The same parts run
+    once more with the dense cold gathers (PR_OPT_HOT_GATHER = 1, test_gpu_hot_gather.py): the 3-byte
+    piece decoder feeding the compaction gives the same bits."""
     rng = np.random.default_rng(78)
     V = 4400000
     src, dst = random_edges(rng, V, 24000000, hub_frac=0.01)
     csr = oracle_c.build_csr(V, src, dst)
     ref = oracle_c.run(csr, 4)
     opts = {"classes": 8}
-    r, infos = _group_ranks(hip, V, src, dst, 2, opts, 4)
-    assert all(i["code_bits"] == 24 for i in infos)
+    r, infos = _group_ranks(hip, V, src, dst, 2, opts, 4, dense_again=True)
+    assert all(i["code_bits"] == 24 and i["hot_gather"] == 0 for i in infos)
     r32, _ = _group_ranks(hip, V, src, dst, 2, dict(opts, codes=0), 4)
     assert max_rel(r, ref["ranks"]) <= RANK_TOL
     assert np.array_equal(r, r32)
@@ -723,11 +738,22 @@ def test_piece_codes_widen(hip, oracle_c):
 def test_compact_codes_widen_then_fall_back(hip, oracle_c, V, bits):
     """Class regions of 2^19..2^20 rows (8 classes over 4.4 M vertices: Q_pad > 2^19) take the
     3-byte codes (kCodeC24: u64 side word, 4 high bits per entry), bitwise the ranks of the 32-bit
-    codes; regions of 2^20 rows or more keep the 32-bit codes.  Both match the oracle."""
+    codes; regions of 2^20 rows or more keep the 32-bit codes.  Both match the oracle.  The 3-byte
+    codes' handle runs once more with the dense cold gathers (PR_OPT_HOT_GATHER = 1,
+    test_gpu_hot_gather.py): the kCodeC24 decoder feeding the compaction gives the same bits."""
     rng = np.random.default_rng(77)
     src, dst = random_edges(rng, V, 4000000, hub_frac=0.01)
+
+    def dense_again(g, ranks):
+        assert g.info()["hot_gather"] == 0
+        g.set_hot_gather(1)
+        assert g.info()["hot_gather"] == 1
+        rd, _ = g.run(4)
+        assert np.array_equal(rd, ranks)
+
     csr, ref, ranks, stats, hist, info = run_both(hip, oracle_c, V, src, dst, 4, layout="split",
-                                                  options={"classes": 8})
+                                                  options={"classes": 8},
+                                                  before_close=dense_again if bits == 24 else None)
     assert info["code_bits"] == bits
     for it in range(4):
         assert max_rel(hist[it], ref["history"][it]) <= RANK_TOL, it

@@ -320,6 +320,32 @@ int pr_batch_get_norms(pr_batch *b, double *dc_out, double *l_out);
 /* pr_get_topk over one column (same order, same exact ties, same bits as pr_batch_get_ranks). */
 int pr_batch_get_topk(pr_batch *b, int32_t column, int32_t k, int32_t *ids_out, double *ranks_out,
                       int32_t *n_out);
+/* Per-column exclusions of the top-K queries.  A column's set names vertices that do not take part
+ * in that column's lists; it affects pr_batch_get_topk and pr_batch_get_topk_all alike (the two never
+ * disagree) and nothing else: the iteration, pr_batch_get_ranks and pr_batch_get_norms do not see
+ * it, and a column without a set behaves bit for bit as before.  A set is valid any time after
+ * create and survives pr_batch_reset.  With a set, column j yields min(k, V - |set_j|) pairs;
+ * excluding every vertex gives 0 pairs and PR_OK.  Memory: one uint16_t per vertex (bit j = "left
+ * out of column j"), allocated with the first non-empty set; an int32 per vertex with the first
+ * pr_batch_get_topk of a column that has a set; the scratch of pr_batch_get_topk_all (histograms, the
+ * candidate buffer and width * k output pairs at most) with its first non-empty result.  All of it
+ * is counted in pr_batch_info's device bytes from then on and freed with the batch; a batch that
+ * calls neither function allocates nothing for them.
+ * Column `column` leaves out ids[0..n) from its top-K queries (both forms below). Replaces the column's
+ * previous set; n == 0 (ids may be NULL) clears it.  Waits for the enqueued steps.  A NULL batch, a
+ * column outside [0, width), n < 0, NULL ids with n > 0, an ID outside [0, V) or a duplicate ID:
+ * PR_ERR_INVALID, checked on the host before any device call, nothing changed; PR_ERR_OOM when the
+ * mask cannot be allocated. */
+int pr_batch_set_exclude(pr_batch *b, int32_t column, int32_t n, const int32_t *ids);
+/* pr_batch_get_topk for every column in one select: column j's list is ids_out / ranks_out[j*k .. j*k + n_out[j]),
+ * n_out has `width` entries.  The order is pr_get_topk's (rank descending by the IEEE bits' order,
+ * ties by original ID ascending, exact inside tie classes), the ranks are the bits
+ * pr_batch_get_ranks returns, and every column's list equals pr_batch_get_topk(b, j, k, ...)'s in
+ * IDs and rank bits.  All columns advance in lockstep over the interleaved rank matrix: one sweep
+ * and one host synchronisation per radix pass for all of them.  k < 0, NULL n_out, NULL ids_out /
+ * ranks_out with k > 0: PR_ERR_INVALID; before pr_batch_reset: PR_ERR_STATE; k == 0: PR_OK and
+ * every n_out[j] == 0.  Waits for the enqueued steps. */
+int pr_batch_get_topk_all(pr_batch *b, int32_t k, int32_t *ids_out, double *ranks_out, int32_t *n_out);
 /* info[i] for i < min(n_info, 7): width, stride, work units, rows split over several units,
  * device bytes held by the batch, iterations done since the last reset, HIP-event time in ns of
  * the iterations of the last pr_batch_step call (-1: none yet, or they are still running). */

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "pr_batch.h"
+#include "pr_batch_topk.h"
 #include "pr_device.h"
 #include "pr_graph.h"
 
@@ -48,6 +49,13 @@ struct pr_batch {
   pr::DevBuf part;       // per workgroup: stride dangling partials, then stride L1 partials
   pr::DevBuf colbuf;     // V doubles: one column, extracted (ranks, top-K) or on its way into T
   pr::TopkState *topk = nullptr;
+  // per-column exclusions of the top-K queries (pr_batch_set_exclude): bit j of mask[v] leaves vertex
+  // v out of column j.  Allocated with the first non-empty set; h_mask is the host's copy.
+  pr::DevBuf excl_mask;  // uint16_t[V]
+  pr::DevBuf excl_oid;   // int32_t[V]: the single-column query's ID array (-1 = excluded), on first need
+  std::vector<uint16_t> h_mask;
+  int64_t n_excl[pr::kBatchMaxWidth] = {0};
+  pr::BTopkState *btopk = nullptr;  // scratch of pr_batch_get_topk_all
   uint32_t vec_mask = 0;  // columns with a teleport vector set
   double teleport = 0.15, damping = 0.85;
   int cur = 0;
@@ -59,13 +67,15 @@ struct pr_batch {
 
   size_t device_bytes() const {
     return units.bytes + long_row.bytes + long_p0.bytes + chunk_part.bytes + R.bytes + T.bytes + C[0].bytes +
-           C[1].bytes + dc[0].bytes + dc[1].bytes + l1.bytes + part.bytes + colbuf.bytes + pr::topk_state_bytes(topk);
+           C[1].bytes + dc[0].bytes + dc[1].bytes + l1.bytes + part.bytes + colbuf.bytes + pr::topk_state_bytes(topk) +
+           excl_mask.bytes + excl_oid.bytes + pr::btopk_state_bytes(btopk);
   }
 };
 
 namespace pr {
 namespace {
 
+static_assert(kBTopkMaxCols == kBatchMaxWidth, "the batch top-K handles every column of a batch");
 constexpr int kBatchGridMax = 8192;  // waves of k_batch_units (a constant: sums must not depend on the device)
 constexpr int kBatchThreads = 256;   // the element-wise kernels
 
@@ -275,6 +285,17 @@ __global__ __launch_bounds__(kBatchThreads) void k_batch_extract(int64_t V, int 
   for (int64_t v = (int64_t)blockIdx.x * kBatchThreads + threadIdx.x; v < V; v += (int64_t)gridDim.x * kBatchThreads)
     out[v] = m[v * S + j];
 }
+// k_batch_extract that also writes the column's ID array for topk_select: v, or -1 where bit j of
+// mask[v] leaves v out of the column.
+__global__ __launch_bounds__(kBatchThreads) void k_batch_extract_excl(int64_t V, int S, int j,
+                                                                      const double *__restrict__ m,
+                                                                      const uint16_t *__restrict__ mask,
+                                                                      double *__restrict__ out, int32_t *__restrict__ oid) {
+  for (int64_t v = (int64_t)blockIdx.x * kBatchThreads + threadIdx.x; v < V; v += (int64_t)gridDim.x * kBatchThreads) {
+    out[v] = m[v * S + j];
+    oid[v] = ((mask[v] >> j) & 1u) ? -1 : (int32_t)v;
+  }
+}
 __global__ __launch_bounds__(kBatchThreads) void k_batch_set_col(int64_t V, int S, int j, const double *__restrict__ in,
                                                                  double value, double *__restrict__ m) {
   for (int64_t v = (int64_t)blockIdx.x * kBatchThreads + threadIdx.x; v < V; v += (int64_t)gridDim.x * kBatchThreads)
@@ -369,6 +390,35 @@ int extract_column(pr_batch *b, int j) {
                      (int64_t)b->V, b->stride, j, b->R.as<double>(), b->colbuf.as<double>());
   PR_HIP(hipGetLastError());
   return PR_OK;
+}
+
+// extract_column for a column with an exclusion set: also fills excl_oid (allocated here).
+int extract_column_excl(pr_batch *b, int j) {
+  if (!b->excl_oid.p) PR_TRY(b->excl_oid.alloc(sizeof(int32_t) * (size_t)std::max<int32_t>(b->V, 1)));
+  hipLaunchKernelGGL(k_batch_extract_excl, dim3(grid_for(b->V, kBatchThreads, 4096)), dim3(kBatchThreads), 0, b->stream,
+                     (int64_t)b->V, b->stride, j, b->R.as<double>(), b->excl_mask.as<uint16_t>(), b->colbuf.as<double>(),
+                     b->excl_oid.as<int32_t>());
+  PR_HIP(hipGetLastError());
+  return PR_OK;
+}
+
+// The device mask the batch top-K reads: nullptr while no column excludes anything.
+const uint16_t *active_mask(const pr_batch *b) {
+  for (int j = 0; j < b->width; ++j)
+    if (b->n_excl[j] > 0) return b->excl_mask.as<uint16_t>();
+  return nullptr;
+}
+
+int topk_all(pr_batch *b, int32_t k, int64_t narrow_div, int32_t *ids_out, double *ranks_out, int32_t *n_out,
+             int32_t *info) {
+  if (!b) return fail(PR_ERR_INVALID, "NULL batch");
+  if (k < 0) return fail(PR_ERR_INVALID, "k < 0");
+  if (narrow_div < 0) return fail(PR_ERR_INVALID, "narrow_div < 0");
+  if (!n_out || (k > 0 && (!ids_out || !ranks_out))) return fail(PR_ERR_INVALID, "NULL argument");
+  if (!b->ready) return fail(PR_ERR_STATE, "pr_batch_get_topk_all before pr_batch_reset");
+  BatchDeviceGuard dg(b->device);
+  return btopk_select(&b->btopk, b->device, b->stream, b->R.as<double>(), b->V, b->width, b->stride, active_mask(b),
+                      b->n_excl, k, narrow_div, ids_out, ranks_out, n_out, info);
 }
 
 int check_column(const pr_batch *b, int32_t column) {
@@ -566,9 +616,65 @@ int pr_batch_get_topk(pr_batch *b, int32_t column, int32_t k, int32_t *ids_out, 
   if (!n_out || (k > 0 && (!ids_out || !ranks_out))) return fail(PR_ERR_INVALID, "NULL argument");
   if (!b->ready) return fail(PR_ERR_STATE, "pr_batch_get_topk before pr_batch_reset");
   pr::BatchDeviceGuard dg(b->device);
+  if (b->n_excl[column] > 0) {  // the excluded vertices are holes of the select
+    PR_TRY(pr::extract_column_excl(b, column));
+    return pr::topk_select(&b->topk, b->device, b->stream, b->colbuf.as<double>(), b->excl_oid.as<int32_t>(), b->V,
+                           b->V - b->n_excl[column], k, pr::kTopkNarrowDiv, ids_out, ranks_out, n_out, nullptr);
+  }
   PR_TRY(pr::extract_column(b, column));
   return pr::topk_select(&b->topk, b->device, b->stream, b->colbuf.as<double>(), nullptr, b->V, b->V, k,
                          pr::kTopkNarrowDiv, ids_out, ranks_out, n_out, nullptr);
+}
+
+int pr_batch_set_exclude(pr_batch *b, int32_t column, int32_t n, const int32_t *ids) {
+  PR_TRY(pr::check_column(b, column));
+  if (n < 0) return fail(PR_ERR_INVALID, "n < 0");
+  if (n > 0 && !ids) return fail(PR_ERR_INVALID, "NULL argument");
+  for (int32_t i = 0; i < n; ++i)
+    if (ids[i] < 0 || ids[i] >= b->V)
+      return fail(PR_ERR_INVALID, "ids[" + std::to_string(i) + "] = " + std::to_string(ids[i]) + " is outside [0, V)");
+  const uint16_t bit = (uint16_t)(1u << column);
+  try {
+    std::vector<uint8_t> seen(n > 0 ? (size_t)b->V : 0, 0);
+    for (int32_t i = 0; i < n; ++i) {
+      if (seen[(size_t)ids[i]]) return fail(PR_ERR_INVALID, "vertex " + std::to_string(ids[i]) + " is listed twice in ids");
+      seen[(size_t)ids[i]] = 1;
+    }
+    if (n > 0 && b->h_mask.empty()) b->h_mask.assign((size_t)b->V, 0);
+  } catch (const std::bad_alloc &) {
+    return fail(PR_ERR_OOM, "host allocation failed");
+  }
+  pr::BatchDeviceGuard dg(b->device);
+  PR_HIP(hipStreamSynchronize(b->stream));
+  if (b->h_mask.empty()) return PR_OK;  // no set was ever stored and this one is empty
+  if (!b->excl_mask.p) PR_TRY(b->excl_mask.alloc(sizeof(uint16_t) * (size_t)b->V));
+  if (b->n_excl[column] > 0)
+    for (uint16_t &m : b->h_mask) m &= (uint16_t)~bit;
+  for (int32_t i = 0; i < n; ++i) b->h_mask[(size_t)ids[i]] |= bit;
+  b->n_excl[column] = n;
+  PR_HIP(hipMemcpyAsync(b->excl_mask.p, b->h_mask.data(), sizeof(uint16_t) * (size_t)b->V, hipMemcpyHostToDevice,
+                        b->stream));
+  PR_HIP(hipStreamSynchronize(b->stream));
+  return PR_OK;
+}
+
+int pr_batch_get_topk_all(pr_batch *b, int32_t k, int32_t *ids_out, double *ranks_out, int32_t *n_out) {
+  return pr::topk_all(b, k, pr::kTopkNarrowDiv, ids_out, ranks_out, n_out, nullptr);
+}
+
+// Internal entry point (not part of include/pagerank_hip.h): pr_batch_get_topk_all with the narrowing
+// divisor as a parameter (0: never narrow) and the pass counts in info[4] (pr_graph.h btopk_select),
+// so that tests reach both sides of the switch at small sizes.
+int pr_batch_topk_all_ex(pr_batch *b, int32_t k, int64_t narrow_div, int32_t *ids_out, double *ranks_out,
+                         int32_t *n_out, int32_t *info) {
+  return pr::topk_all(b, k, narrow_div, ids_out, ranks_out, n_out, info);
+}
+
+// Internal: the summed HIP-event time in ns of the kernels of the last pr_batch_topk_all_ex call (-1: none).
+int pr_batch_topk_all_kernel_ns(const pr_batch *b, int64_t *ns_out) {
+  if (!b || !ns_out) return fail(PR_ERR_INVALID, "NULL argument");
+  *ns_out = pr::btopk_kernel_ns(b->btopk);
+  return PR_OK;
 }
 
 int pr_batch_info(const pr_batch *b, int64_t *info, int32_t n_info) {
@@ -590,6 +696,8 @@ void pr_batch_destroy(pr_batch *b) {
   if (b->stream) (void)hipStreamSynchronize(b->stream);
   pr::topk_state_free(b->topk);
   b->topk = nullptr;
+  pr::btopk_state_free(b->btopk);
+  b->btopk = nullptr;
   if (b->ev0) (void)hipEventDestroy(b->ev0);
   if (b->ev1) (void)hipEventDestroy(b->ev1);
   hipStream_t s = b->stream;

@@ -286,4 +286,21 @@ int topk_select(TopkState **state, int device, hipStream_t s, const double *r, c
                 int32_t *info);
 size_t topk_state_bytes(const TopkState *t);
 void topk_state_free(TopkState *t);
+// Batch top-K (pr_batch_topk.hip): the lists of all `width` columns of the interleaved V x stride
+// rank matrix R from one lockstep select; waits for s first.  mask (device, V entries, or nullptr:
+// nothing excluded): bit j of mask[v] leaves vertex v out of column j; n_excl[j] = the bits set for
+// column j.  Column j's n_out[j] = min(k, V - n_excl[j]) pairs go to ids_out / ranks_out[j * k ..).
+// narrow_div: the candidates are compacted once the active columns hold at most V * width /
+// narrow_div together (0: never).  info (may be NULL): {histogram passes, those over R, those over
+// the compacted candidates, digits known when the candidates were compacted or -1}.  *state
+// (scratch) is created on first use with a non-empty result.
+struct BTopkState;
+int btopk_select(BTopkState **state, int device, hipStream_t s, const double *R, int64_t V, int width, int stride,
+                 const uint16_t *mask, const int64_t *n_excl, int64_t k, int64_t narrow_div, int32_t *ids_out,
+                 double *ranks_out, int32_t *n_out, int32_t *info);
+// HIP-event time in ns of the kernels of the last call that passed a non-NULL info (their sum,
+// without the host's work between the passes); -1: none yet.
+int64_t btopk_kernel_ns(const BTopkState *t);
+size_t btopk_state_bytes(const BTopkState *t);
+void btopk_state_free(BTopkState *t);
 }  // namespace pr

@@ -3,7 +3,7 @@
 //   pagerank <input-path> [iterations=10] [--format=edges|ccjson] [--out DIR]
 //            [--save-every-iter] [--dangling=local|none] [--device N] [--quiet] [--stats]
 //            [--resume DIR/PageRank<i>] [--devices D0,D1,...] [--top K] [--seeds FILE]
-//            [--seed-set FILE]...
+//            [--seed-set FILE]... [--exclude-seeds]
 //
 // Input (libpagerank_host): "src dst" edge list ("src" alone = record without links), or
 // --format=ccjson "url<TAB>json" Common Crawl metadata records (Sparky.java:61-123).  URLs are
@@ -33,9 +33,14 @@
 // --seeds and gives one personalised ranking; all of them run as one batch (pr_batch_*), one pass
 // over the graph per iteration for all sets.  Per set, in command-line order, the listing is a line
 // "# seed set <j>: <FILE>" followed by that set's "<url> has rank: <r>." lines (with --top K its K
-// best, pr_batch_get_topk); --out DIR writes DIR/seedset<j>/PageRank<last>/part-00000 + _SUCCESS.
+// best; the listings of all sets come from one select, pr_batch_get_topk_all); --out DIR writes
+// DIR/seedset<j>/PageRank<last>/part-00000 + _SUCCESS.
 // Not with --seeds, --devices, --resume or --save-every-iter (usage errors, before any GPU work).
 //   pagerank edges.txt 20 --seed-set alice.txt --seed-set bob.txt --top 100
+// --exclude-seeds (needs --seed-set and --top, else a usage error before any GPU work): every set's
+// own seed URLs are left out of that set's --top listing (pr_batch_set_exclude); part files from
+// --out stay complete.
+//   pagerank edges.txt 20 --seed-set alice.txt --seed-set bob.txt --top 100 --exclude-seeds
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -52,6 +57,7 @@ struct Options {
   int iterations = 10;  // Sparky.java:187
   int format = PRH_FORMAT_EDGES;
   bool save_every = false, quiet = false, stats = false;
+  bool exclude_seeds = false;  // --exclude-seeds
   uint32_t flags = PR_DANGLING_LOCAL;
   int device = 0;
   int top = 0;  // --top K (0: list every URL)
@@ -80,7 +86,9 @@ std::vector<int> parse_devices(const std::string &s) {
                "                [--save-every-iter] [--dangling=local|none] [--device N] [--quiet] [--stats]\n"
                "                [--resume DIR/PageRank<i>] [--devices D0,D1,...] [--top K] [--seeds FILE]\n"
                "                [--seed-set FILE]...  (1 to 16 seed files, run as one batch; not with --seeds,\n"
-               "                --devices, --resume or --save-every-iter)\n");
+               "                --devices, --resume or --save-every-iter)\n"
+               "                [--exclude-seeds]  (with --seed-set and --top: a set's own seeds are left out of\n"
+               "                its listing)\n");
   std::exit(2);
 }
 
@@ -96,6 +104,7 @@ Options parse(int argc, char **argv) {
     else if (a == "--save-every-iter") o.save_every = true;
     else if (a == "--quiet") o.quiet = true;
     else if (a == "--stats") o.stats = true;
+    else if (a == "--exclude-seeds") o.exclude_seeds = true;
     else if (a == "--dangling=local") o.flags = PR_DANGLING_LOCAL;
     else if (a == "--dangling=none") o.flags = PR_DANGLING_NONE;
     else if (a == "--device" && i + 1 < argc) o.device = std::atoi(argv[++i]);
@@ -123,6 +132,7 @@ Options parse(int argc, char **argv) {
   }
   if (o.path.empty()) usage("missing input path");
   if (o.iterations < 0) usage("iterations must be >= 0");
+  if (o.exclude_seeds && (o.seed_sets.empty() || o.top == 0)) usage("--exclude-seeds needs --seed-set and --top");
   if (!o.seed_sets.empty()) {
     if (!o.seeds.empty()) usage("--seeds and --seed-set are exclusive");
     if (o.seed_sets.size() > 16) usage("--seed-set: at most 16 seed sets");
@@ -232,8 +242,13 @@ int run_seed_sets(const Options &o, const prh_edges *edges, const std::vector<Se
   int error = 0;
   std::vector<double> ranks((size_t)V + 1);
   const int32_t top_k = o.top < V ? o.top : V;
-  std::vector<int32_t> top_ids((size_t)top_k + 1);
-  std::vector<double> top_ranks((size_t)top_k + 1);
+  // --top: the listings of all sets from one select, set j's pairs at j * top_k
+  const bool listed = o.top > 0 && !o.quiet;
+  std::vector<int32_t> top_ids(listed ? (size_t)top_k * sets.size() + 1 : 1), top_n(sets.size() + 1);
+  std::vector<double> top_ranks(top_ids.size());
+  for (size_t j = 0; j < sets.size() && rc == PR_OK && o.exclude_seeds; ++j)  // a set's own seeds never appear in its listing
+    rc = pr_batch_set_exclude(b, (int32_t)j, sets[j].n, sets[j].ids);
+  if (rc == PR_OK && listed) rc = pr_batch_get_topk_all(b, top_k, top_ids.data(), top_ranks.data(), top_n.data());
   for (size_t j = 0; j < sets.size() && rc == PR_OK; ++j) {
     const bool full = !o.out.empty() || (o.top == 0 && !o.quiet);
     if (full) rc = pr_batch_get_ranks(b, (int32_t)j, ranks.data());
@@ -247,9 +262,8 @@ int run_seed_sets(const Options &o, const prh_edges *edges, const std::vector<Se
     std::fflush(stdout);
     int rc_out = 0;
     if (o.top > 0) {
-      int32_t n = 0;
-      rc = pr_batch_get_topk(b, (int32_t)j, top_k, top_ids.data(), top_ranks.data(), &n);
-      if (rc == PR_OK) rc_out = prh_write_has_rank_ids(edges, nullptr, top_ids.data(), top_ranks.data(), n);
+      rc_out = prh_write_has_rank_ids(edges, nullptr, top_ids.data() + j * (size_t)top_k, top_ranks.data() + j * (size_t)top_k,
+                                      top_n[j]);
     } else {
       rc_out = prh_write_has_rank(edges, nullptr, ranks.data());
     }

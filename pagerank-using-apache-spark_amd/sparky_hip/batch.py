@@ -5,7 +5,9 @@ one pass streams the graph's column indices once for all of them.  Every column 
 teleport vector (``set_teleport`` / ``set_teleport_sparse``; a column without one uses the scalar
 of ``reset``) and runs exactly the iteration ``PageRankGraph.set_teleport`` documents.  The graph
 must be a single part that kept its canonical CSR; the batch borrows it, so close the batch first
-(the context manager does).
+(the context manager does).  ``topk_all(k)`` returns every column's top-K list from one select over
+all columns; ``set_exclude(column, ids)`` leaves vertices (a seed set, known items) out of a
+column's lists.
 """
 from __future__ import annotations
 
@@ -90,6 +92,45 @@ class PageRankBatch:
         n = ctypes.c_int32(0)
         check(_lib.load().pr_batch_get_topk(self._h, int(column), k, _ptr(ids), _ptr(rk), ctypes.byref(n)))
         return ids[: n.value], rk[: n.value]
+
+    def set_exclude(self, column: int, ids) -> None:
+        """pr_batch_set_exclude: the vertices ``ids`` do not take part in ``column``'s top-K lists
+        (``topk`` and ``topk_all`` alike); replaces the column's previous set, an empty ``ids`` (or
+        None) clears it.  Ranks, norms and the iteration never see it; it survives reset()."""
+        i = np.zeros(0, np.int32) if ids is None else np.ascontiguousarray(ids, dtype=np.int32)
+        if i.ndim != 1:
+            raise ValueError("ids must be a 1-D array")
+        check(_lib.load().pr_batch_set_exclude(self._h, int(column), int(i.shape[0]), _ptr(i) if i.shape[0] else None))
+
+    def topk_all(self, k: int):
+        """pr_batch_get_topk_all: every column's top-K from one lockstep select; a list of ``width``
+        pairs (ids int32[n_j], ranks float64[n_j]), each equal to ``topk(j, k)``."""
+        return self._topk_all(k, None)[0]
+
+    def _topk_all_ex(self, k: int, narrow_div: int):
+        """The library's internal entry point behind topk_all(): the same query with the narrowing
+        divisor as a parameter (the candidates are compacted once the active columns hold at most
+        V * width / narrow_div together; 0: never).  Returns (lists, info) with info = {passes,
+        matrix_passes, cand_passes, narrowed_at, kernel_ns}.  For tests and tools/batch_topk_bench.py."""
+        return self._topk_all(k, int(narrow_div))
+
+    def _topk_all(self, k: int, narrow_div):
+        k = int(k)
+        ids, rk = np.zeros(max(k, 1) * self.width, np.int32), np.zeros(max(k, 1) * self.width, np.float64)
+        n = np.zeros(self.width, np.int32)
+        info = np.zeros(4, np.int32)
+        L = _lib.load()
+        if narrow_div is None:
+            check(L.pr_batch_get_topk_all(self._h, k, _ptr(ids), _ptr(rk), _ptr(n)))
+        else:
+            check(L.pr_batch_topk_all_ex(self._h, k, narrow_div, _ptr(ids), _ptr(rk), _ptr(n), _ptr(info)))
+        lists = [(ids[j * k: j * k + int(n[j])].copy(), rk[j * k: j * k + int(n[j])].copy()) for j in range(self.width)]
+        out = dict(zip(("passes", "matrix_passes", "cand_passes", "narrowed_at"), (int(x) for x in info)))
+        if narrow_div is not None:  # the summed HIP-event time of the call's kernels (-1: it launched none)
+            ns = ctypes.c_int64(-1)
+            check(L.pr_batch_topk_all_kernel_ns(self._h, ctypes.byref(ns)))
+            out["kernel_ns"] = ns.value
+        return lists, out
 
     def info(self) -> dict:
         a = np.zeros(len(_lib.BATCH_INFO_NAMES), np.int64)

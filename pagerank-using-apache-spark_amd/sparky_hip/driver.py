@@ -2,7 +2,8 @@
 
 CLI: ``python -m sparky_hip <input-path> [iterations=10] [--format edges|ccjson]
 [--out DIR] [--save-every-iter] [--dangling=local|none] [--device N] [--quiet]
-[--resume DIR/PageRank<i>] [--devices D0,D1,...] [--top K] [--seeds FILE] [--seed-set FILE]...``
+[--resume DIR/PageRank<i>] [--devices D0,D1,...] [--top K] [--seeds FILE] [--seed-set FILE]...
+[--exclude-seeds]``
 
 * input: text edge list, ``src dst`` per line; a single-token line ``src`` is a record without
   ``a`` links (Sparky.java:114-118).  Tokens (URLs) are taken verbatim and interned to dense
@@ -32,7 +33,11 @@ CLI: ``python -m sparky_hip <input-path> [iterations=10] [--form
   ``<url> has rank: <r>.`` lines (with ``--top K`` its K best); ``--out DIR`` writes
   ``DIR/seedset<j>/PageRank<last>/part-00000`` + ``_SUCCESS``.  Not with ``--seeds``,
   ``--devices``, ``--resume`` or ``--save-every-iter`` (usage errors, before any GPU work).  Same
-  bytes as the C++ CLI.
+  bytes as the C++ CLI.  With ``--top K`` the listings of all sets come from one select
+  (``PageRankBatch.topk_all``).
+* ``--exclude-seeds`` (needs ``--seed-set`` and ``--top``, else a usage error before any GPU work):
+  every set's own seed URLs are left out of that set's ``--top`` listing
+  (``PageRankBatch.set_exclude``); part files from ``--out`` stay complete.
 """
 from __future__ import annotations
 
@@ -187,6 +192,11 @@ def _run_seed_sets(edges, a, sets, top, out) -> None:
             for it in range(a.iterations):
                 out.write(f"Starting iter{it}\n")
                 b.step(1)
+            if a.exclude_seeds:  # a set's own seeds never appear in its listing
+                for j, (ids, _) in enumerate(sets):
+                    b.set_exclude(j, ids)
+            # the listings of all sets from one select (PageRankBatch.topk_all)
+            tops = b.topk_all(min(top, edges.n_vertices)) if top and not a.quiet else None
             for j in range(len(sets)):
                 ranks = b.ranks(j) if a.out or (not top and not a.quiet) else None
                 if a.out and a.iterations > 0:
@@ -196,7 +206,7 @@ def _run_seed_sets(edges, a, sets, top, out) -> None:
                 out.write(f"# seed set {j}: {a.seed_set[j]}\n")
                 out.flush()
                 if top:
-                    edges.write_has_rank_ids(None, *b.topk(j, top))
+                    edges.write_has_rank_ids(None, *tops[j])
                 else:
                     edges.write_has_rank(None, ranks)
 
@@ -223,7 +233,11 @@ def main(argv=None) -> int:
     ap.add_argument("--seed-set", action="append", default=None, metavar="FILE",
                     help="batched personalised PageRank: 1 to 16 seed files, run as one batch; not with --seeds, "
                          "--devices, --resume or --save-every-iter")
+    ap.add_argument("--exclude-seeds", action="store_true",
+                    help="with --seed-set and --top: a set's own seed URLs are left out of its listing")
     a = ap.parse_args(argv)
+    if a.exclude_seeds and not (a.seed_set and a.top is not None):
+        ap.error("--exclude-seeds needs --seed-set and --top")
     if a.top is not None and a.top < 1:
         ap.error("--top takes a count K >= 1")
     top = a.top or 0

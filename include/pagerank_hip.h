@@ -312,10 +312,35 @@ int pr_batch_set_teleport_sparse(pr_batch *b, int32_t column, int32_t n, const i
 int pr_batch_reset(pr_batch *b, double teleport, double damping, const double *init_ranks);
 /* Enqueues `iterations` iterations of every column; no host sync between iterations. */
 int pr_batch_step(pr_batch *b, int32_t iterations);
+/* Iterates until every column has converged or `max_iterations` iterations have run, deciding per
+ * column on the device.  Every call starts with all `width` columns active.  After each iteration
+ * a column whose L1 delta l1_j = sum_v |r'_j[v] - r_j[v]| (the value pr_batch_get_norms reports)
+ * satisfies l1_j <= tol is frozen for the rest of the call: its ranks, contributions,
+ * next-iteration dangling sum and L1 no longer change.  The test is absolute, on Sparky's
+ * unnormalised ranks (they sum to about V, not to 1: scale tol accordingly), and a NaN L1 never
+ * satisfies it; tol == 0 freezes a column only on an L1 of exactly 0.
+ * iters_out (`width` entries, may be NULL): the iterations applied to column j in this call,
+ * max_iterations for a column that did not converge.  Column j ends bitwise where
+ * pr_batch_step(b, iters_out[j]) from the same state ends (a column's bits do not depend on its
+ * neighbours), and pr_batch_get_norms afterwards reports per column the dc used by and the L1 of
+ * that column's last applied iteration, bitwise those values too -- so l1_j <= tol says whether
+ * column j converged.  The batch is left in an ordinary state: a later pr_batch_step(b, m) advances
+ * every column, the frozen ones included, by m iterations.  pr_batch_info's iteration count grows
+ * by the count of the column that advanced furthest.  Top-K queries and exclusions are unaffected.
+ * The call is synchronous: it returns when the result is final.  Iterations are enqueued in blocks;
+ * between iterations there is no host synchronisation except one read-back of a few words per
+ * block, and once every column is frozen the rest of a block returns at kernel entry.  The result
+ * does not depend on the block size.  The few words per column this needs on the device are part
+ * of pr_batch_info's device bytes.
+ * A NULL batch, max_iterations < 0, a tol that is NaN, negative or infinite: PR_ERR_INVALID, checked
+ * before any device call; before pr_batch_reset: PR_ERR_STATE; max_iterations == 0: PR_OK, every
+ * iters_out[j] == 0, nothing changes. */
+int pr_batch_step_until(pr_batch *b, int32_t max_iterations, double tol, int32_t *iters_out);
 int pr_batch_sync(pr_batch *b);
 /* Column `column`: V doubles in original-ID order.  Waits for the enqueued steps. */
 int pr_batch_get_ranks(pr_batch *b, int32_t column, double *ranks_out);
-/* `width` doubles each: per column the dc used by the last iteration and its L1 delta. */
+/* `width` doubles each: per column the dc used by the last iteration and its L1 delta (after
+ * pr_batch_step_until: of that column's own last applied iteration). */
 int pr_batch_get_norms(pr_batch *b, double *dc_out, double *l_out);
 /* pr_get_topk over one column (same order, same exact ties, same bits as pr_batch_get_ranks). */
 int pr_batch_get_topk(pr_batch *b, int32_t column, int32_t k, int32_t *ids_out, double *ranks_out,

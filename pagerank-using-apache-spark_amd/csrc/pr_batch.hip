@@ -21,6 +21,16 @@
 // a column's dangling mass -- has an order that depends on the graph and the stride only.  No
 // floating-point atomics anywhere.
 //
+// pr_batch_step_until runs the same iteration through sibling kernels (k_batch_units_until,
+// k_batch_long_until, k_batch_finalize_until) that read an active mask (pr_batch_until.h) from
+// device memory.  A column whose bit is clear is frozen: its lanes still take part in every row sum, shuffle and barrier, but
+// store no rank, no L1 and no new dangling sum; instead they copy their contributions cin -> cout and
+// the finalize step copies dc_in -> dc_out, so that both double buffers stay valid whatever the
+// parity of the iteration the column stopped at.  A fourth, one-thread launch (k_batch_decide) runs
+// after the finalize step, counts the iteration for the active columns and clears the bits of those
+// whose L1 is within tol; no kernel of an iteration can therefore see that iteration's own decision.
+// With an empty mask every kernel returns at entry.  pr_batch_step launches none of these.
+//
 // The batch only reads the graph's canon_* buffers; it launches none of the graph's kernels and
 // owns its stream and all its state.
 #include <algorithm>
@@ -31,6 +41,7 @@
 
 #include "pr_batch.h"
 #include "pr_batch_topk.h"
+#include "pr_batch_until.h"
 #include "pr_device.h"
 #include "pr_graph.h"
 
@@ -47,6 +58,11 @@ struct pr_batch {
   pr::DevBuf R, T, C[2];
   pr::DevBuf dc[2], l1;  // stride doubles each; dc[cur] is what the next iteration reads
   pr::DevBuf part;       // per workgroup: stride dangling partials, then stride L1 partials
+  // pr_batch_step_until: the device's BatchUntilState, and per column the dc its last applied
+  // iteration of the call used (stride doubles; pr_batch_get_norms reads it while until_norms is set)
+  pr::DevBuf until, dcu;
+  pr::BatchUntilState h_until{};
+  bool until_norms = false;
   pr::DevBuf colbuf;     // V doubles: one column, extracted (ranks, top-K) or on its way into T
   pr::TopkState *topk = nullptr;
   // per-column exclusions of the top-K queries (pr_batch_set_exclude): bit j of mask[v] leaves vertex
@@ -68,7 +84,7 @@ struct pr_batch {
   size_t device_bytes() const {
     return units.bytes + long_row.bytes + long_p0.bytes + chunk_part.bytes + R.bytes + T.bytes + C[0].bytes +
            C[1].bytes + dc[0].bytes + dc[1].bytes + l1.bytes + part.bytes + colbuf.bytes + pr::topk_state_bytes(topk) +
-           excl_mask.bytes + excl_oid.bytes + pr::btopk_state_bytes(btopk);
+           until.bytes + dcu.bytes + excl_mask.bytes + excl_oid.bytes + pr::btopk_state_bytes(btopk);
   }
 };
 
@@ -134,6 +150,14 @@ __device__ __forceinline__ void update_elem(const BatchArgs &a, int64_t v, int64
   if (d > 0) a.cout[p] = __ddiv_rn(rn, (double)d);
   else if ((f & PR_VF_SINK) && !a.dangling_none) dcp = __dadd_rn(dcp, rn);
   l1p = __dadd_rn(l1p, fabs(rn - rold));
+}
+
+// update_elem under an active mask: an element of a frozen column (act == false) only carries its
+// contribution over to the buffer the next iteration reads (d == 0 elements are 0 in both buffers).
+__device__ __forceinline__ void update_elem_until(const BatchArgs &a, int64_t v, int64_t p, double Sv, double rold,
+                                                  uint32_t f, double tdc, bool act, double &dcp, double &l1p) {
+  if (act) update_elem(a, v, p, Sv, rold, f, tdc, dcp, l1p);
+  else if (a.deg[v] > 0) a.cout[p] = a.cin[p];
 }
 
 template <int S>
@@ -253,6 +277,139 @@ __global__ __launch_bounds__(kBatchThreads) void k_batch_finalize(const double *
   if (threadIdx.x == 0) (kind ? l1_out : dc_out)[j] = acc;
 }
 
+// ---- pr_batch_step_until's siblings of the three kernels above --------------------------------
+// The same statements in the same order (kept apart so that the kernels pr_batch_step launches
+// compile exactly as before), plus: the mask word read at entry, and update_elem_until in place of
+// update_elem.  Everything that shuffles or waits at a barrier runs for frozen columns too.
+template <int S>
+__global__ __launch_bounds__(kWave) void k_batch_units_until(BatchArgs a, const BatchUntilState *__restrict__ us) {
+  constexpr int G = kWave / S;
+  __shared__ double sS[kBatchUnitRows * S];
+  const uint32_t m = us->mask;  // one word, the same for every lane: a uniform exit
+  if (m == 0) return;
+  const int lane = threadIdx.x, g = lane / S, j = lane % S;
+  const bool act = (m >> j) & 1u;
+  const double tdc = a.dc[j] / a.n_vertices;
+  double dcp = 0.0, l1p = 0.0;
+  for (int64_t u = blockIdx.x; u < a.n_units; u += gridDim.x) {
+    const BatchUnit un = a.units[u];
+    if (un.rows < 0) {  // CHUNK
+      const double acc = row_sum<S>(a.col, a.cin, un.e0, un.e0 + un.n, g, j);
+      if (lane < S) a.chunk_part[(int64_t)un.slot * S + j] = acc;
+      continue;
+    }
+    const int rows = un.rows;
+    const long long rp_l = (long long)a.rowptr[(int64_t)un.row0 + (lane < rows ? lane : rows)];
+    const int64_t uend = un.e0 + un.n;
+    for (int k0 = 0; k0 < rows; k0 += G) {  // short rows
+      const int k = k0 + g;
+      const int ks = k < rows ? k : 0;
+      const int64_t b = __shfl(rp_l, ks, kWave);
+      const int64_t e1 = __shfl(rp_l, ks + 1 < kWave ? ks + 1 : kWave - 1, kWave);
+      const int64_t deg = k < rows ? (ks + 1 < rows ? e1 : uend) - b : 0;
+      if (deg > 0 && deg <= kBatchShortRow) {
+        int32_t c[kBatchShortRow];
+        double x[kBatchShortRow];
+#pragma unroll
+        for (int q = 0; q < kBatchShortRow; ++q) c[q] = q < deg ? a.col[b + q] : 0;
+#pragma unroll
+        for (int q = 0; q < kBatchShortRow; ++q) x[q] = q < deg ? a.cin[(int64_t)c[q] * S + j] : 0.0;
+        double acc = 0.0;
+#pragma unroll
+        for (int q = 0; q < kBatchShortRow; ++q)
+          if (q < deg) acc = __dadd_rn(acc, x[q]);
+        sS[k * S + j] = acc;
+      }
+    }
+    for (int k = 0; k < rows; ++k) {  // longer rows
+      const int64_t b = __shfl(rp_l, k, kWave);
+      const int64_t e = k + 1 < rows ? (int64_t)__shfl(rp_l, k + 1, kWave) : uend;
+      if (e - b <= kBatchShortRow) continue;
+      const double acc = row_sum<S>(a.col, a.cin, b, e, g, j);
+      if (lane < S) sS[k * S + j] = acc;
+    }
+    __syncthreads();
+    const int total = rows * S;
+    for (int idx = lane; idx < total; idx += kWave) {
+      const int64_t v = (int64_t)un.row0 + idx / S, p = v * S + j;
+      const uint32_t f = a.vflags[v];
+      const double rold = a.r[p];
+      update_elem_until(a, v, p, (f & PR_VF_INDEG0) ? rold : sS[idx], rold, f, tdc, act, dcp, l1p);
+    }
+    __syncthreads();
+  }
+  dcp = group_sum<S>(dcp);
+  l1p = group_sum<S>(l1p);
+  if (lane < S) {  // a frozen column's partials are zeros that k_batch_finalize_until never reads
+    a.part[((int64_t)blockIdx.x * 2) * S + j] = dcp;
+    a.part[((int64_t)blockIdx.x * 2 + 1) * S + j] = l1p;
+  }
+}
+
+template <int S>
+__global__ __launch_bounds__(kBatchThreads) void k_batch_long_until(BatchArgs a, const int32_t *__restrict__ long_row,
+                                                                    const int32_t *__restrict__ long_p0, int64_t n_long,
+                                                                    int64_t part_block0,
+                                                                    const BatchUntilState *__restrict__ us) {
+  const uint32_t m = us->mask;
+  if (m == 0) return;  // uniform, and before the barrier of block_col_part
+  const int64_t idx = (int64_t)blockIdx.x * kBatchThreads + threadIdx.x;
+  const int64_t q = idx / S;
+  const int j = threadIdx.x % S;
+  double dcp = 0.0, l1p = 0.0;
+  if (q < n_long) {
+    const int32_t p0 = long_p0[q], p1 = long_p0[q + 1];
+    double acc = 0.0;
+    for (int32_t k = p0; k < p1; ++k) acc = __dadd_rn(acc, a.chunk_part[(int64_t)k * S + j]);
+    const int64_t v = long_row[q], p = v * S + j;
+    update_elem_until(a, v, p, acc, a.r[p], a.vflags[v], a.dc[j] / a.n_vertices, (m >> j) & 1u, dcp, l1p);
+  }
+  block_col_part<S>(dcp, l1p, a.part, part_block0 + blockIdx.x);
+}
+
+// k_batch_finalize under an active mask.  An active column also records the dc this iteration used
+// (dcu); a frozen one -- padding columns are never in the mask -- keeps its L1 and carries its
+// next-iteration dc across the swap.  The mask is only read here: k_batch_decide changes it.
+__global__ __launch_bounds__(kBatchThreads) void k_batch_finalize_until(const double *__restrict__ part, int64_t n_blocks,
+                                                                        int S, const double *__restrict__ dc_in,
+                                                                        double *__restrict__ dc_out,
+                                                                        double *__restrict__ l1_out,
+                                                                        double *__restrict__ dcu,
+                                                                        const BatchUntilState *__restrict__ us) {
+  __shared__ double red[kBatchThreads / kWave];
+  const uint32_t m = us->mask;
+  if (m == 0) return;
+  const int kind = blockIdx.x / S, j = blockIdx.x % S;
+  if (!((m >> j) & 1u)) {  // the whole workgroup: no barrier is skipped by a part of it
+    if (kind == 0 && threadIdx.x == 0) dc_out[j] = dc_in[j];
+    return;
+  }
+  double acc = 0.0;
+  for (int64_t b = threadIdx.x; b < n_blocks; b += kBatchThreads) acc = __dadd_rn(acc, part[(b * 2 + kind) * S + j]);
+  acc = block_sum<kBatchThreads>(acc, red);
+  if (threadIdx.x == 0) {
+    if (kind) {
+      l1_out[j] = acc;
+    } else {
+      dc_out[j] = acc;
+      dcu[j] = dc_in[j];
+    }
+  }
+}
+
+// One thread, after both workgroups of every column have finished: the iteration counts for the
+// columns it advanced, and the mask the next iteration runs under.
+__global__ __launch_bounds__(kWave) void k_batch_decide(BatchUntilState *__restrict__ us, const double *__restrict__ l1,
+                                                        double tol, int width) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const uint32_t m = us->mask;
+  if (m == 0) return;
+  for (int j = 0; j < width; ++j)
+    if ((m >> j) & 1u) ++us->iters[j];
+  ++us->executed;
+  us->mask = batch_until_decide(m, l1, tol, width);
+}
+
 // Ranks to init (or 1.0) in every column, the scalar teleport into the columns without a vector,
 // the contributions of those ranks, zeros into the padding columns; per-workgroup dangling partials.
 // gridDim.x * kBatchThreads is a multiple of S, so a thread stays in column threadIdx.x % S.
@@ -351,6 +508,32 @@ int launch_iteration(pr_batch *b) {
   return PR_OK;
 }
 
+// One iteration of pr_batch_step_until, reading the buffers of parity `cur` (the host's b->cur moves
+// only once the executed count is known).
+template <int S>
+int launch_iteration_until(pr_batch *b, int cur, double tol) {
+  BatchArgs a = batch_args(b);
+  a.cin = b->C[cur].as<double>();
+  a.cout = b->C[cur ^ 1].as<double>();
+  a.dc = b->dc[cur].as<double>();
+  const BatchUntilState *us = b->until.as<BatchUntilState>();
+  hipLaunchKernelGGL(k_batch_units_until<S>, dim3(b->ugrid), dim3(kWave), 0, b->stream, a, us);
+  PR_HIP(hipGetLastError());
+  if (b->n_long > 0) {
+    hipLaunchKernelGGL(k_batch_long_until<S>, dim3(b->lgrid), dim3(kBatchThreads), 0, b->stream, a,
+                       b->long_row.as<int32_t>(), b->long_p0.as<int32_t>(), b->n_long, (int64_t)b->ugrid, us);
+    PR_HIP(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_batch_finalize_until, dim3(2 * S), dim3(kBatchThreads), 0, b->stream, b->part.as<double>(),
+                     (int64_t)b->ugrid + b->lgrid, S, b->dc[cur].as<double>(), b->dc[cur ^ 1].as<double>(),
+                     b->l1.as<double>(), b->dcu.as<double>(), us);
+  PR_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_batch_decide, dim3(1), dim3(kWave), 0, b->stream, b->until.as<BatchUntilState>(),
+                     b->l1.as<double>(), tol, b->width);
+  PR_HIP(hipGetLastError());
+  return PR_OK;
+}
+
 template <int S>
 int launch_reset(pr_batch *b, const double *d_init) {
   const pr_graph *g = b->g;
@@ -421,6 +604,44 @@ int topk_all(pr_batch *b, int32_t k, int64_t narrow_div, int32_t *ids_out, doubl
                       b->n_excl, k, narrow_div, ids_out, ranks_out, n_out, info);
 }
 
+// pr_batch_step_until with the block size as a parameter; info (may be NULL): iterations enqueued,
+// iterations executed.
+int step_until(pr_batch *b, int32_t max_iterations, double tol, int32_t block, int32_t *iters_out, int32_t *info) {
+  if (!b) return fail(PR_ERR_INVALID, "NULL batch");
+  if (max_iterations < 0) return fail(PR_ERR_INVALID, "max_iterations < 0");
+  if (!(tol >= 0.0) || std::isinf(tol)) return fail(PR_ERR_INVALID, "tol must be a finite number >= 0");
+  if (block < 1) return fail(PR_ERR_INVALID, "block < 1");
+  if (!b->ready) return fail(PR_ERR_STATE, "pr_batch_step_until before pr_batch_reset");
+  if (info) info[0] = info[1] = 0;
+  if (max_iterations == 0) {
+    if (iters_out) std::fill(iters_out, iters_out + b->width, 0);
+    return PR_OK;
+  }
+  BatchDeviceGuard dg(b->device);
+  BatchUntilState &h = b->h_until;
+  h = BatchUntilState{};
+  h.mask = batch_until_all(b->width);
+  PR_HIP(hipMemcpyAsync(b->until.p, &h, sizeof(h), hipMemcpyHostToDevice, b->stream));
+  int32_t enq = 0;
+  while (enq < max_iterations && h.mask != 0) {
+    const int32_t n = std::min(block, max_iterations - enq);
+    for (int32_t i = 0; i < n; ++i, ++enq) PR_TRY(PR_BATCH_DISPATCH(launch_iteration_until, b, b->cur ^ (enq & 1), tol));
+    // the one read-back per block: the mask, the executed count and the per-column counts
+    PR_HIP(hipMemcpyAsync(&h, b->until.p, sizeof(h), hipMemcpyDeviceToHost, b->stream));
+    PR_HIP(hipStreamSynchronize(b->stream));
+  }
+  // the iterations past the last active column's returned at entry: parity and count follow the device
+  b->cur ^= h.executed & 1;
+  b->iters_done += h.executed;
+  if (h.executed > 0) b->until_norms = true;
+  if (iters_out) std::copy(h.iters, h.iters + b->width, iters_out);
+  if (info) {
+    info[0] = enq;
+    info[1] = h.executed;
+  }
+  return PR_OK;
+}
+
 int check_column(const pr_batch *b, int32_t column) {
   if (!b) return fail(PR_ERR_INVALID, "NULL batch");
   if (column < 0 || column >= b->width)
@@ -465,6 +686,8 @@ int build_batch(pr_batch *b) {
   // the reset's grid is at most kBatchGridMax workgroups, an iteration's ugrid + lgrid
   PR_TRY(b->part.alloc(sizeof(double) * 2 * S * ((size_t)kBatchGridMax + (size_t)b->lgrid)));
   PR_TRY(b->colbuf.alloc(sizeof(double) * V));
+  PR_TRY(b->until.alloc(sizeof(BatchUntilState)));
+  PR_TRY(b->dcu.alloc(sizeof(double) * S));
   return PR_OK;
 }
 
@@ -553,6 +776,7 @@ int pr_batch_reset(pr_batch *b, double teleport, double damping, const double *i
   PR_HIP(hipStreamSynchronize(b->stream));  // init_ranks is borrowed for the call only
   b->cur = 0;
   b->iters_done = 0;
+  b->until_norms = false;
   b->ready = true;
   return PR_OK;
 }
@@ -561,7 +785,10 @@ int pr_batch_step(pr_batch *b, int32_t iterations) {
   if (!b || iterations < 0) return fail(PR_ERR_INVALID, "NULL batch or iterations < 0");
   if (!b->ready) return fail(PR_ERR_STATE, "pr_batch_step before pr_batch_reset");
   pr::BatchDeviceGuard dg(b->device);
-  if (iterations > 0) PR_HIP(hipEventRecord(b->ev0, b->stream));
+  if (iterations > 0) {
+    PR_HIP(hipEventRecord(b->ev0, b->stream));
+    b->until_norms = false;  // every column advances: the last iteration's dc is dc[cur ^ 1] again
+  }
   for (int32_t it = 0; it < iterations; ++it) {
     PR_TRY(PR_BATCH_DISPATCH(pr::launch_iteration, b));
     b->cur ^= 1;
@@ -572,6 +799,18 @@ int pr_batch_step(pr_batch *b, int32_t iterations) {
     b->timed = true;
   }
   return PR_OK;
+}
+
+int pr_batch_step_until(pr_batch *b, int32_t max_iterations, double tol, int32_t *iters_out) {
+  return pr::step_until(b, max_iterations, tol, pr::kUntilBlock, iters_out, nullptr);
+}
+
+// Internal entry point (not part of include/pagerank_hip.h): pr_batch_step_until with the number of
+// iterations enqueued between two read-backs as a parameter (>= 1), and info[2] = {iterations
+// enqueued, iterations executed}, so that tests can show that the result does not depend on it.
+int pr_batch_step_until_ex(pr_batch *b, int32_t max_iterations, double tol, int32_t block, int32_t *iters_out,
+                           int32_t *info) {
+  return pr::step_until(b, max_iterations, tol, block, iters_out, info);
 }
 
 int pr_batch_sync(pr_batch *b) {
@@ -598,8 +837,9 @@ int pr_batch_get_norms(pr_batch *b, double *dc_out, double *l_out) {
   if (!b->ready) return fail(PR_ERR_STATE, "pr_batch_get_norms before pr_batch_reset");
   pr::BatchDeviceGuard dg(b->device);
   double dc[pr::kBatchMaxWidth], l1[pr::kBatchMaxWidth];
-  // the dc *used* by the last iteration lives in the previous buffer (none run: the reset's)
-  const pr::DevBuf &used = b->dc[b->iters_done > 0 ? b->cur ^ 1 : b->cur];
+  // the dc *used* by the last iteration lives in the previous buffer (none run: the reset's); after
+  // pr_batch_step_until the columns stopped at different iterations and dcu holds each one's
+  const pr::DevBuf &used = b->until_norms ? b->dcu : b->dc[b->iters_done > 0 ? b->cur ^ 1 : b->cur];
   PR_HIP(hipMemcpyAsync(dc, used.p, sizeof(double) * b->stride, hipMemcpyDeviceToHost, b->stream));
   PR_HIP(hipMemcpyAsync(l1, b->l1.p, sizeof(double) * b->stride, hipMemcpyDeviceToHost, b->stream));
   PR_HIP(hipStreamSynchronize(b->stream));

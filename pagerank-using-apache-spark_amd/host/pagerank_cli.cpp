@@ -3,7 +3,7 @@
 //   pagerank <input-path> [iterations=10] [--format=edges|ccjson] [--out DIR]
 //            [--save-every-iter] [--dangling=local|none] [--device N] [--quiet] [--stats]
 //            [--resume DIR/PageRank<i>] [--devices D0,D1,...] [--top K] [--seeds FILE]
-//            [--seed-set FILE]... [--exclude-seeds]
+//            [--seed-set FILE]... [--exclude-seeds] [--tol X]
 //
 // Input (libpagerank_host): "src dst" edge list ("src" alone = record without links), or
 // --format=ccjson "url<TAB>json" Common Crawl metadata records (Sparky.java:61-123).  URLs are
@@ -41,7 +41,17 @@
 // own seed URLs are left out of that set's --top listing (pr_batch_set_exclude); part files from
 // --out stay complete.
 //   pagerank edges.txt 20 --seed-set alice.txt --seed-set bob.txt --top 100 --exclude-seeds
+// --tol X (needs --seed-set, else a usage error before any GPU work; X a finite number >= 0): every
+// set stops at its own convergence, decided on the GPU (pr_batch_step_until): a set is done after the
+// first iteration whose L1 delta, on the unnormalised ranks, is at most X, and the iterations argument
+// becomes the cap.  "Starting iter<i>" is printed for every i below the largest count; after each
+// "# seed set <j>: <FILE>" line comes "# iterations: <n_j> (converged)" or "(not converged)"; --out
+// writes set j to DIR/seedset<j>/PageRank<n_j - 1>.  Each listing is that of the same command without
+// --tol run for exactly n_j iterations.
+//   pagerank edges.txt 500 --seed-set alice.txt --seed-set bob.txt --top 100 --tol 1e-6
+#include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -58,6 +68,8 @@ struct Options {
   int format = PRH_FORMAT_EDGES;
   bool save_every = false, quiet = false, stats = false;
   bool exclude_seeds = false;  // --exclude-seeds
+  bool has_tol = false;        // --tol X: `iterations` is the cap
+  double tol = 0.0;
   uint32_t flags = PR_DANGLING_LOCAL;
   int device = 0;
   int top = 0;  // --top K (0: list every URL)
@@ -88,7 +100,9 @@ std::vector<int> parse_devices(const std::string &s) {
                "                [--seed-set FILE]...  (1 to 16 seed files, run as one batch; not with --seeds,\n"
                "                --devices, --resume or --save-every-iter)\n"
                "                [--exclude-seeds]  (with --seed-set and --top: a set's own seeds are left out of\n"
-               "                its listing)\n");
+               "                its listing)\n"
+               "                [--tol X]  (with --seed-set: every set stops once its L1 delta is <= X; iterations\n"
+               "                is the cap)\n");
   std::exit(2);
 }
 
@@ -124,6 +138,13 @@ Options parse(int argc, char **argv) {
         usage("--top takes a count K >= 1");
       o.top = std::atoi(t.c_str());
     }
+    else if ((a == "--tol" && i + 1 < argc) || a.rfind("--tol=", 0) == 0) {
+      const std::string t = a == "--tol" ? std::string(argv[++i]) : a.substr(6);
+      char *end = nullptr;
+      o.tol = std::strtod(t.c_str(), &end);
+      if (t.empty() || *end != '\0' || !std::isfinite(o.tol) || !(o.tol >= 0.0)) usage("--tol: not a finite number >= 0");
+      o.has_tol = true;
+    }
     else if (a == "-h" || a == "--help") usage(nullptr);
     else if (!a.empty() && a[0] == '-') usage(("unknown option " + a).c_str());
     else if (pos == 0) { o.path = a; ++pos; }
@@ -133,6 +154,7 @@ Options parse(int argc, char **argv) {
   if (o.path.empty()) usage("missing input path");
   if (o.iterations < 0) usage("iterations must be >= 0");
   if (o.exclude_seeds && (o.seed_sets.empty() || o.top == 0)) usage("--exclude-seeds needs --seed-set and --top");
+  if (o.has_tol && o.seed_sets.empty()) usage("--tol needs --seed-set");
   if (!o.seed_sets.empty()) {
     if (!o.seeds.empty()) usage("--seeds and --seed-set are exclusive");
     if (o.seed_sets.size() > 16) usage("--seed-set: at most 16 seed sets");
@@ -235,9 +257,21 @@ int run_seed_sets(const Options &o, const prh_edges *edges, const std::vector<Se
   for (size_t j = 0; j < sets.size() && rc == PR_OK; ++j)
     rc = pr_batch_set_teleport_sparse(b, (int32_t)j, sets[j].n, sets[j].ids, sets[j].values.data(), 0.0);
   if (rc == PR_OK) rc = pr_batch_reset(b, 0.15, 0.85, nullptr);
-  for (int it = 0; it < o.iterations && rc == PR_OK; ++it) {
-    std::printf("Starting iter%d\n", it);
-    rc = pr_batch_step(b, 1);
+  // iterations applied to every set: the argument, or with --tol each set's own count (the cap at most)
+  std::vector<int32_t> n_it(sets.size(), o.iterations);
+  std::vector<char> converged(sets.size(), 0);
+  if (o.has_tol) {
+    if (rc == PR_OK) rc = pr_batch_step_until(b, o.iterations, o.tol, n_it.data());
+    double dc[16], l1[16];
+    if (rc == PR_OK) rc = pr_batch_get_norms(b, dc, l1);
+    for (size_t j = 0; j < sets.size() && rc == PR_OK; ++j) converged[j] = n_it[j] > 0 && l1[j] <= o.tol;
+    const int32_t most = rc == PR_OK ? *std::max_element(n_it.begin(), n_it.end()) : 0;
+    for (int32_t it = 0; it < most; ++it) std::printf("Starting iter%d\n", it);
+  } else {
+    for (int it = 0; it < o.iterations && rc == PR_OK; ++it) {
+      std::printf("Starting iter%d\n", it);
+      rc = pr_batch_step(b, 1);
+    }
   }
   int error = 0;
   std::vector<double> ranks((size_t)V + 1);
@@ -252,13 +286,14 @@ int run_seed_sets(const Options &o, const prh_edges *edges, const std::vector<Se
   for (size_t j = 0; j < sets.size() && rc == PR_OK; ++j) {
     const bool full = !o.out.empty() || (o.top == 0 && !o.quiet);
     if (full) rc = pr_batch_get_ranks(b, (int32_t)j, ranks.data());
-    if (rc == PR_OK && !o.out.empty() && o.iterations > 0 &&
-        prh_write_part(edges, (o.out + "/seedset" + std::to_string(j)).c_str(), o.iterations - 1, ranks.data()) != 0) {
+    if (rc == PR_OK && !o.out.empty() && n_it[j] > 0 &&
+        prh_write_part(edges, (o.out + "/seedset" + std::to_string(j)).c_str(), n_it[j] - 1, ranks.data()) != 0) {
       std::fprintf(stderr, "pagerank: %s\n", prh_last_error());
       error = 1;
     }
     if (rc != PR_OK || o.quiet) continue;
     std::printf("# seed set %zu: %s\n", j, o.seed_sets[j].c_str());
+    if (o.has_tol) std::printf("# iterations: %d (%s)\n", n_it[j], converged[j] ? "converged" : "not converged");
     std::fflush(stdout);
     int rc_out = 0;
     if (o.top > 0) {

@@ -63,7 +63,7 @@ EXPORTED = [
     "pr_set_teleport", "pr_set_teleport_sparse",
     "pr_batch_create", "pr_batch_set_teleport", "pr_batch_set_teleport_sparse", "pr_batch_reset", "pr_batch_step",
     "pr_batch_sync", "pr_batch_get_ranks", "pr_batch_get_norms", "pr_batch_get_topk", "pr_batch_info",
-    "pr_batch_destroy", "pr_batch_set_exclude", "pr_batch_get_topk_all",
+    "pr_batch_destroy", "pr_batch_set_exclude", "pr_batch_get_topk_all", "pr_batch_step_until",
 ]
 # pr_batch_info, in order
 BATCH_INFO_NAMES = ["width", "stride", "n_units", "n_long_rows", "device_bytes", "iters", "last_step_ns"]
@@ -150,11 +150,14 @@ def load() -> ctypes.CDLL:
         "pr_batch_destroy": ([P], None),
         "pr_batch_set_exclude": ([P, i32, i32, P], ctypes.c_int),
         "pr_batch_get_topk_all": ([P, i32, P, P, P], ctypes.c_int),
+        "pr_batch_step_until": ([P, i32, dbl, P], ctypes.c_int),
         # internal (not in the header): pr_get_topk / pr_batch_get_topk_all with the narrowing threshold
         # and the pass counts
         "pr_topk_select_ex": ([P, i32, i64, P, P, P, P], ctypes.c_int),
         "pr_batch_topk_all_ex": ([P, i32, i64, P, P, P, P], ctypes.c_int),
         "pr_batch_topk_all_kernel_ns": ([P, P], ctypes.c_int),  # HIP-event kernel time of the last _ex call
+        # internal: pr_batch_step_until with the block size and the enqueued / executed iteration counts
+        "pr_batch_step_until_ex": ([P, i32, dbl, i32, P, P], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

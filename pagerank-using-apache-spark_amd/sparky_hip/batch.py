@@ -7,7 +7,8 @@ of ``reset``) and runs exactly the iteration ``PageRankGraph.set_teleport`` docu
 must be a single part that kept its canonical CSR; the batch borrows it, so close the batch first
 (the context manager does).  ``topk_all(k)`` returns every column's top-K list from one select over
 all columns; ``set_exclude(column, ids)`` leaves vertices (a seed set, known items) out of a
-column's lists.
+column's lists.  ``step_until(max_iterations, tol)`` stops every column at its own convergence, decided
+on the device.
 """
 from __future__ import annotations
 
@@ -69,6 +70,25 @@ class PageRankBatch:
     def step(self, iterations: int) -> None:
         check(_lib.load().pr_batch_step(self._h, int(iterations)))
 
+    def step_until(self, max_iterations: int, tol: float) -> np.ndarray:
+        """pr_batch_step_until: iterate until every column's L1 delta is at most ``tol`` (absolute, on
+        the unnormalised ranks) or ``max_iterations`` have run; a column that gets there is frozen on
+        the device for the rest of the call, bitwise where ``step(iters[j])`` would leave it.
+        Returns int32[width], the iterations applied to each column (``max_iterations``: not
+        converged; ``norms()`` then shows its L1 above ``tol``).  Synchronous."""
+        iters = np.zeros(self.width, np.int32)
+        check(_lib.load().pr_batch_step_until(self._h, int(max_iterations), float(tol), _ptr(iters)))
+        return iters
+
+    def _step_until_ex(self, max_iterations: int, tol: float, block: int):
+        """The library's internal entry point behind step_until(): the same call with the number of
+        iterations enqueued between two read-backs as a parameter.  Returns (iters, info) with
+        info = (iterations enqueued, iterations executed).  For tests and tools/batch_until_bench.py."""
+        iters, info = np.zeros(self.width, np.int32), np.zeros(2, np.int32)
+        check(_lib.load().pr_batch_step_until_ex(self._h, int(max_iterations), float(tol), int(block), _ptr(iters),
+                                                 _ptr(info)))
+        return iters, (int(info[0]), int(info[1]))
+
     def sync(self) -> None:
         check(_lib.load().pr_batch_sync(self._h))
 
@@ -80,7 +100,7 @@ class PageRankBatch:
 
     def norms(self):
         """(dc, l1): float64[width] each -- per column the dangling sum the last iteration used and
-        the L1 distance it moved the ranks."""
+        the L1 distance it moved the ranks (after step_until: of each column's own last iteration)."""
         dc, l1 = np.zeros(self.width, np.float64), np.zeros(self.width, np.float64)
         check(_lib.load().pr_batch_get_norms(self._h, _ptr(dc), _ptr(l1)))
         return dc, l1

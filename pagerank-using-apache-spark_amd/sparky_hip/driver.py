@@ -3,7 +3,7 @@
 CLI: ``python -m sparky_hip <input-path> [iterations=10] [--format edges|ccjson]
 [--out DIR] [--save-every-iter] [--dangling=local|none] [--device N] [--quiet]
 [--resume DIR/PageRank<i>] [--devices D0,D1,...] [--top K] [--seeds FILE] [--seed-set FILE]...
-[--exclude-seeds]``
+[--exclude-seeds] [--tol X]``
 
 * input: text edge list, ``src dst`` per line; a single-token line ``src`` is a record without
   ``a`` links (Sparky.java:114-118).  Tokens (URLs) are taken verbatim and interned to dense
@@ -38,6 +38,13 @@ CLI: ``python -m sparky_hip <input-path> [iterations=10] [--form
 * ``--exclude-seeds`` (needs ``--seed-set`` and ``--top``, else a usage error before any GPU work):
   every set's own seed URLs are left out of that set's ``--top`` listing
   (``PageRankBatch.set_exclude``); part files from ``--out`` stay complete.
+* ``--tol X`` (needs ``--seed-set``, else a usage error before any GPU work; X a finite number >= 0):
+  every set stops at its own convergence, decided on the GPU (``PageRankBatch.step_until``): a set is
+  done after the first iteration whose L1 delta, on the unnormalised ranks, is at most X, and the
+  iterations argument becomes the cap.  ``Starting iter<i>`` is printed for every i below the largest
+  count; after each ``# seed set <j>: <FILE>`` line comes ``# iterations: <n_j> (converged)`` or
+  ``(not converged)``; ``--out`` writes set j to ``DIR/seedset<j>/PageRank<n_j - 1>``.  Same bytes as
+  the C++ CLI.
 """
 from __future__ import annotations
 
@@ -189,9 +196,18 @@ def _run_seed_sets(edges, a, sets, top, out) -> None:
             for j, (ids, values) in enumerate(sets):
                 b.set_teleport_sparse(j, ids, values)
             b.reset()
-            for it in range(a.iterations):
-                out.write(f"Starting iter{it}\n")
-                b.step(1)
+            # iterations applied to every set: the argument, or with --tol each set's own count
+            n_it = [a.iterations] * len(sets)
+            if a.tol is not None:
+                n_it = [int(n) for n in b.step_until(a.iterations, a.tol)]
+                _, l1 = b.norms()
+                converged = [n > 0 and x <= a.tol for n, x in zip(n_it, l1.tolist())]
+                for it in range(max(n_it)):
+                    out.write(f"Starting iter{it}\n")
+            else:
+                for it in range(a.iterations):
+                    out.write(f"Starting iter{it}\n")
+                    b.step(1)
             if a.exclude_seeds:  # a set's own seeds never appear in its listing
                 for j, (ids, _) in enumerate(sets):
                     b.set_exclude(j, ids)
@@ -199,11 +215,13 @@ def _run_seed_sets(edges, a, sets, top, out) -> None:
             tops = b.topk_all(min(top, edges.n_vertices)) if top and not a.quiet else None
             for j in range(len(sets)):
                 ranks = b.ranks(j) if a.out or (not top and not a.quiet) else None
-                if a.out and a.iterations > 0:
-                    edges.write_part(os.path.join(a.out, f"seedset{j}"), a.iterations - 1, ranks)
+                if a.out and n_it[j] > 0:
+                    edges.write_part(os.path.join(a.out, f"seedset{j}"), n_it[j] - 1, ranks)
                 if a.quiet:
                     continue
                 out.write(f"# seed set {j}: {a.seed_set[j]}\n")
+                if a.tol is not None:
+                    out.write(f"# iterations: {n_it[j]} ({'converged' if converged[j] else 'not converged'})\n")
                 out.flush()
                 if top:
                     edges.write_has_rank_ids(None, *tops[j])
@@ -235,7 +253,18 @@ def main(argv=None) -> int:
                          "--devices, --resume or --save-every-iter")
     ap.add_argument("--exclude-seeds", action="store_true",
                     help="with --seed-set and --top: a set's own seed URLs are left out of its listing")
+    ap.add_argument("--tol", default=None, metavar="X",
+                    help="with --seed-set: every set stops once its L1 delta is <= X; iterations is the cap")
     a = ap.parse_args(argv)
+    if a.tol is not None:
+        try:
+            a.tol = float(a.tol)
+        except ValueError:
+            a.tol = math.nan
+        if not (math.isfinite(a.tol) and a.tol >= 0.0):
+            ap.error("--tol: not a finite number >= 0")
+        if not a.seed_set:
+            ap.error("--tol needs --seed-set")
     if a.exclude_seeds and not (a.seed_set and a.top is not None):
         ap.error("--exclude-seeds needs --seed-set and --top")
     if a.top is not None and a.top < 1:

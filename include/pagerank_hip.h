@@ -336,6 +336,75 @@ int pr_batch_step(pr_batch *b, int32_t iterations);
  * before any device call; before pr_batch_reset: PR_ERR_STATE; max_iterations == 0: PR_OK, every
  * iters_out[j] == 0, nothing changes. */
 int pr_batch_step_until(pr_batch *b, int32_t max_iterations, double tol, int32_t *iters_out);
+/* Restarts column `column` alone: its ranks become init_ranks (NULL: 1.0; V doubles in original-ID
+ * order), with the scalar teleport and damping of the last pr_batch_reset and the column's teleport
+ * vector as it stands.  Afterwards the column holds bit for bit what it holds after pr_batch_reset
+ * with the same arguments in a batch of the same width -- ranks, contributions, dangling sum (formed
+ * in pr_batch_reset's order of summation) -- and every later iteration of it equals that batch's;
+ * every other column, the padding included, is bitwise unaffected, now and later.  Valid at either
+ * parity of the iteration count and after pr_batch_step or pr_batch_step_until* alike.
+ * pr_batch_get_norms then reports for the column the dangling sum of init_ranks and an L1 of 0, the
+ * other columns' norms unchanged.  pr_batch_info's iteration count does not move.  Waits for the
+ * enqueued steps.  Like pr_batch_reset, the call does not check init_ranks for non-finite entries.
+ * A NULL batch, a column outside [0, width): PR_ERR_INVALID; before pr_batch_reset: PR_ERR_STATE. */
+int pr_batch_reset_column(pr_batch *b, int32_t column, const double *init_ranks);
+/* pr_batch_step_until for the columns of the bit mask `active` only, ending at the first
+ * convergence.  Columns outside `active` are frozen for the whole call, ranks and norms.  After
+ * every iteration an active column with l1_j <= tol (pr_batch_step_until's test) has converged; the
+ * call returns after the first iteration in which at least one did, else after max_iterations.
+ * *executed_out: the iterations applied (the same for every active column); *converged_out: the
+ * columns that converged in the last of them, 0 at the cap.  Every active column ends bitwise where
+ * pr_batch_step(b, executed) would leave it; pr_batch_get_norms follows pr_batch_step_until's rules;
+ * pr_batch_info's iteration count grows by `executed`.  Synchronous.  Iterations are enqueued in
+ * blocks with one read-back per block; the device itself stops the rest of a block once a column
+ * has converged (those launches return at kernel entry), and the result does not depend on the
+ * block size.
+ * A NULL batch or output, max_iterations < 0, a tol that is NaN, negative or infinite, an `active`
+ * bit at or above width: PR_ERR_INVALID; before pr_batch_reset: PR_ERR_STATE; active == 0 or
+ * max_iterations == 0: PR_OK, executed = 0, converged = 0, nothing changes. */
+int pr_batch_step_until_any(pr_batch *b, uint32_t active, int32_t max_iterations, double tol,
+                            int32_t *executed_out, uint32_t *converged_out);
+/* A queue of seed sets served by the batch's `width` columns: a column whose query is done hands
+ * over its result and starts the next query of the queue in the following iteration, while the
+ * others carry on undisturbed.
+ * A query is a sparse teleport vector (as pr_batch_set_teleport_sparse) and an exclusion set for its
+ * top-K list (as pr_batch_set_exclude; n_exclude == 0: none).  Every query is checked on the host
+ * by those calls' rules before any device call: one bad query fails the call with PR_ERR_INVALID
+ * and changes nothing.  No table of V entries is built per query, and a refill moves 12 bytes per
+ * seed to the device (plus one upload of the exclusion mask, 2 V bytes, for all the columns refilled
+ * together, when one of their queries or of the queries they replace has a set).
+ * Queries enter the columns in queue order (query q in column q for q < width).  A query starts
+ * from pr_batch_reset_column(column, init_ranks) with its own vector and runs until l1 <= tol or
+ * until it has had max_iterations iterations of its own.  When queries finish in an iteration,
+ * `done` (may be NULL) runs for each on the calling thread in ascending column order: `iterations`
+ * is the query's count, `converged` whether it met tol, `l1` its last L1.  The column still holds
+ * the result: inside the callback, and only there, pr_batch_get_ranks, pr_batch_get_topk (it honours
+ * the query's exclusion set) and pr_batch_get_norms may be called on the batch; every other call on
+ * the handle returns PR_ERR_STATE.  Freed columns then take the next queries in order; with fewer
+ * queries left than columns the spare columns do not iterate.  Returns when every query has been
+ * reported.
+ * A query's iteration count and rank bits do not depend on the column it ran in, on when it
+ * started or on what ran beside it: they equal those of a fresh batch of the same width after
+ * pr_batch_reset, the vector in column 0 and pr_batch_step(iterations).  The order of the callbacks
+ * is a function of the queries' iteration counts, width and max_iterations only.
+ * Afterwards the batch is in an ordinary state: pr_batch_step advances all columns; the columns keep
+ * the teleport vectors and exclusion sets of the last queries they served (spare columns: what they
+ * had before).
+ * A NULL batch, n_queries < 0, NULL queries with n_queries > 0, max_iterations < 1, a bad tol:
+ * PR_ERR_INVALID; before pr_batch_reset: PR_ERR_STATE; n_queries == 0: PR_OK. */
+typedef struct pr_batch_query {
+  int32_t n_seeds;
+  const int32_t *ids;
+  const double *values;
+  double rest;
+  int32_t n_exclude;
+  const int32_t *exclude;
+} pr_batch_query;
+typedef void (*pr_batch_done_cb)(int32_t query, int32_t column, int32_t iterations, int32_t converged,
+                                 double l1, void *user);
+int pr_batch_run_queue(pr_batch *b, int32_t n_queries, const pr_batch_query *queries,
+                       int32_t max_iterations, double tol, const double *init_ranks,
+                       pr_batch_done_cb done, void *user);
 int pr_batch_sync(pr_batch *b);
 /* Column `column`: V doubles in original-ID order.  Waits for the enqueued steps. */
 int pr_batch_get_ranks(pr_batch *b, int32_t column, double *ranks_out);

@@ -31,6 +31,13 @@
 // whose L1 is within tol; no kernel of an iteration can therefore see that iteration's own decision.
 // With an empty mask every kernel returns at entry.  pr_batch_step launches none of these.
 //
+// pr_batch_run_queue (scheduler: pr_batch_queue.h) refills columns one at a time: k_batch_set_col and
+// k_batch_scatter_col write a sparse teleport vector into T on the device, k_batch_reset_col and
+// k_batch_finalize_col restart one column in k_batch_reset's order of summation, and
+// pr_batch_step_until_any runs the *_until kernels under the mask of the occupied columns with
+// k_batch_decide_any in k_batch_decide's place, which empties the mask after the first iteration in
+// which a column converged.
+//
 // The batch only reads the graph's canon_* buffers; it launches none of the graph's kernels and
 // owns its stream and all its state.
 #include <algorithm>
@@ -41,6 +48,7 @@
 
 #include "pr_batch.h"
 #include "pr_batch_topk.h"
+#include "pr_batch_queue.h"
 #include "pr_batch_until.h"
 #include "pr_device.h"
 #include "pr_graph.h"
@@ -62,6 +70,7 @@ struct pr_batch {
   // iteration of the call used (stride doubles; pr_batch_get_norms reads it while until_norms is set)
   pr::DevBuf until, dcu;
   pr::BatchUntilState h_until{};
+  pr::BatchQueueState h_queue{};
   bool until_norms = false;
   pr::DevBuf colbuf;     // V doubles: one column, extracted (ranks, top-K) or on its way into T
   pr::TopkState *topk = nullptr;
@@ -72,6 +81,12 @@ struct pr_batch {
   std::vector<uint16_t> h_mask;
   int64_t n_excl[pr::kBatchMaxWidth] = {0};
   pr::BTopkState *btopk = nullptr;  // scratch of pr_batch_get_topk_all
+  // pr_batch_step_until_any / pr_batch_run_queue: the device's BatchQueueState; a query's seed IDs
+  // and values on their way into T (grown on demand); the queue's init_ranks (V doubles, on first
+  // need: colbuf is taken by the queries of the done callback)
+  pr::DevBuf qstate, qids, qvals, qinit;
+  std::vector<int32_t> excl_ids[pr::kBatchMaxWidth];  // the IDs behind n_excl, to clear a set in O(n)
+  bool in_done_cb = false;  // pr_batch_run_queue is inside its callback: only the three getters run
   uint32_t vec_mask = 0;  // columns with a teleport vector set
   double teleport = 0.15, damping = 0.85;
   int cur = 0;
@@ -84,13 +99,16 @@ struct pr_batch {
   size_t device_bytes() const {
     return units.bytes + long_row.bytes + long_p0.bytes + chunk_part.bytes + R.bytes + T.bytes + C[0].bytes +
            C[1].bytes + dc[0].bytes + dc[1].bytes + l1.bytes + part.bytes + colbuf.bytes + pr::topk_state_bytes(topk) +
-           until.bytes + dcu.bytes + excl_mask.bytes + excl_oid.bytes + pr::btopk_state_bytes(btopk);
+           until.bytes + dcu.bytes + excl_mask.bytes + excl_oid.bytes + pr::btopk_state_bytes(btopk) + qstate.bytes +
+           qids.bytes + qvals.bytes + qinit.bytes;
   }
 };
 
 namespace pr {
 namespace {
 
+constexpr const char *kInDoneCb =
+    "inside pr_batch_run_queue's callback only pr_batch_get_ranks, pr_batch_get_topk and pr_batch_get_norms may be called";
 static_assert(kBTopkMaxCols == kBatchMaxWidth, "the batch top-K handles every column of a batch");
 constexpr int kBatchGridMax = 8192;  // waves of k_batch_units (a constant: sums must not depend on the device)
 constexpr int kBatchThreads = 256;   // the element-wise kernels
@@ -410,6 +428,21 @@ __global__ __launch_bounds__(kWave) void k_batch_decide(BatchUntilState *__restr
   us->mask = batch_until_decide(m, l1, tol, width);
 }
 
+// k_batch_decide for pr_batch_step_until_any: the same counting, but the mask only ever changes to 0
+// -- after the first iteration in which an active column converged (batch_any_decide), so that the
+// remaining launches of the block return at entry.
+__global__ __launch_bounds__(kWave) void k_batch_decide_any(BatchUntilState *__restrict__ us,
+                                                            BatchQueueState *__restrict__ qs,
+                                                            const double *__restrict__ l1, double tol, int width) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const uint32_t m = us->mask;
+  if (m == 0) return;
+  for (int j = 0; j < width; ++j)
+    if ((m >> j) & 1u) ++us->iters[j];
+  ++us->executed;
+  us->mask = batch_any_decide(m, l1, tol, width, qs);
+}
+
 // Ranks to init (or 1.0) in every column, the scalar teleport into the columns without a vector,
 // the contributions of those ranks, zeros into the padding columns; per-workgroup dangling partials.
 // gridDim.x * kBatchThreads is a multiple of S, so a thread stays in column threadIdx.x % S.
@@ -434,6 +467,72 @@ __global__ __launch_bounds__(kBatchThreads) void k_batch_reset(int64_t V, int wi
     if (d == 0 && (vflags[v] & PR_VF_SINK) && !dangling_none) dcp = __dadd_rn(dcp, x);
   }
   block_col_part<S>(dcp, 0.0, part, blockIdx.x);
+}
+
+// k_batch_reset for column j alone, launched with k_batch_reset's grid: the threads of column j
+// (threadIdx.x % S == j) visit the elements they visit there, in the same order, so a thread's
+// dangling partial has the same bits; the others only wait at the barrier.  T stays as it is.  Both
+// contribution buffers get the new contributions (the column may be frozen in the next iteration,
+// which copies cin -> cout only where out_deg > 0).  The workgroup's sum, in block_col_part's order,
+// goes to part1[blockIdx.x]: a dense array of its own shape in the part scratch, which no iteration
+// is using (the caller has waited for the stream).
+template <int S>
+__global__ __launch_bounds__(kBatchThreads) void k_batch_reset_col(int64_t V, int j, const double *__restrict__ init,
+                                                                   const int32_t *__restrict__ deg,
+                                                                   const uint8_t *__restrict__ vflags, int dangling_none,
+                                                                   double *__restrict__ r, double *__restrict__ c0,
+                                                                   double *__restrict__ c1, double *__restrict__ part1) {
+  __shared__ double sh[kBatchThreads];
+  const int t = threadIdx.x;
+  double dcp = 0.0;
+  if (t % S == j)
+    for (int64_t p = (int64_t)blockIdx.x * kBatchThreads + t; p < V * S; p += (int64_t)gridDim.x * kBatchThreads) {
+      const int64_t v = p / S;
+      const double x = init ? init[v] : 1.0;
+      r[p] = x;
+      const int32_t d = deg[v];
+      const double c = d > 0 ? __ddiv_rn(x, (double)d) : 0.0;
+      c0[p] = c;
+      c1[p] = c;
+      if (d == 0 && (vflags[v] & PR_VF_SINK) && !dangling_none) dcp = __dadd_rn(dcp, x);
+    }
+  sh[t] = dcp;
+  __syncthreads();
+  if (t == 0) {
+    double x = 0.0;
+    for (int k = j; k < kBatchThreads; k += S) x = __dadd_rn(x, sh[k]);
+    part1[blockIdx.x] = x;
+  }
+}
+
+// k_batch_finalize's dangling workgroup for one column over part1: the same strided sums and the
+// same block_sum.  The sum goes to both dc buffers (either may be read next, and a frozen column
+// copies one to the other) and to dcu, so that pr_batch_get_norms finds it whatever advanced the
+// batch last; the column's L1 is the 0 that k_batch_finalize sums after a reset.
+__global__ __launch_bounds__(kBatchThreads) void k_batch_finalize_col(const double *__restrict__ part1, int64_t n_blocks,
+                                                                      int j, double *__restrict__ dc0,
+                                                                      double *__restrict__ dc1, double *__restrict__ dcu,
+                                                                      double *__restrict__ l1) {
+  __shared__ double red[kBatchThreads / kWave];
+  double acc = 0.0;
+  for (int64_t b = threadIdx.x; b < n_blocks; b += kBatchThreads) acc = __dadd_rn(acc, part1[b]);
+  acc = block_sum<kBatchThreads>(acc, red);
+  if (threadIdx.x == 0) {
+    dc0[j] = acc;
+    dc1[j] = acc;
+    dcu[j] = acc;
+    l1[j] = 0.0;
+  }
+}
+
+// m[ids[i] * S + j] = values[i]: the seeds of a sparse teleport vector, after k_batch_set_col has
+// written `rest` everywhere.  The host has checked that the IDs are distinct and inside [0, V).
+__global__ __launch_bounds__(kBatchThreads) void k_batch_scatter_col(int32_t n, int S, int j,
+                                                                     const int32_t *__restrict__ ids,
+                                                                     const double *__restrict__ values,
+                                                                     double *__restrict__ m) {
+  for (int64_t i = (int64_t)blockIdx.x * kBatchThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBatchThreads)
+    m[(int64_t)ids[i] * S + j] = values[i];
 }
 
 // Column j of m (V x S) from / to V contiguous doubles.
@@ -509,9 +608,9 @@ int launch_iteration(pr_batch *b) {
 }
 
 // One iteration of pr_batch_step_until, reading the buffers of parity `cur` (the host's b->cur moves
-// only once the executed count is known).
+// only once the executed count is known).  any: the decision is pr_batch_step_until_any's.
 template <int S>
-int launch_iteration_until(pr_batch *b, int cur, double tol) {
+int launch_iteration_until(pr_batch *b, int cur, double tol, bool any) {
   BatchArgs a = batch_args(b);
   a.cin = b->C[cur].as<double>();
   a.cout = b->C[cur ^ 1].as<double>();
@@ -528,8 +627,29 @@ int launch_iteration_until(pr_batch *b, int cur, double tol) {
                      (int64_t)b->ugrid + b->lgrid, S, b->dc[cur].as<double>(), b->dc[cur ^ 1].as<double>(),
                      b->l1.as<double>(), b->dcu.as<double>(), us);
   PR_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_batch_decide, dim3(1), dim3(kWave), 0, b->stream, b->until.as<BatchUntilState>(),
-                     b->l1.as<double>(), tol, b->width);
+  if (any)
+    hipLaunchKernelGGL(k_batch_decide_any, dim3(1), dim3(kWave), 0, b->stream, b->until.as<BatchUntilState>(),
+                       b->qstate.as<BatchQueueState>(), b->l1.as<double>(), tol, b->width);
+  else
+    hipLaunchKernelGGL(k_batch_decide, dim3(1), dim3(kWave), 0, b->stream, b->until.as<BatchUntilState>(),
+                       b->l1.as<double>(), tol, b->width);
+  PR_HIP(hipGetLastError());
+  return PR_OK;
+}
+
+// Enqueues the restart of column j from d_init (V doubles on the device; nullptr: 1.0).  The caller
+// has waited for the stream: the part scratch is free.
+template <int S>
+int launch_reset_column(pr_batch *b, int j, const double *d_init) {
+  const pr_graph *g = b->g;
+  const unsigned grid = grid_for((int64_t)b->V * S, kBatchThreads, kBatchGridMax);  // k_batch_reset's
+  hipLaunchKernelGGL(k_batch_reset_col<S>, dim3(grid), dim3(kBatchThreads), 0, b->stream, (int64_t)b->V, j, d_init,
+                     g->canon_deg.as<int32_t>(), g->canon_vflags.as<uint8_t>(), b->dangling_none ? 1 : 0,
+                     b->R.as<double>(), b->C[0].as<double>(), b->C[1].as<double>(), b->part.as<double>());
+  PR_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_batch_finalize_col, dim3(1), dim3(kBatchThreads), 0, b->stream, b->part.as<double>(),
+                     (int64_t)grid, j, b->dc[0].as<double>(), b->dc[1].as<double>(), b->dcu.as<double>(),
+                     b->l1.as<double>());
   PR_HIP(hipGetLastError());
   return PR_OK;
 }
@@ -598,6 +718,7 @@ int topk_all(pr_batch *b, int32_t k, int64_t narrow_div, int32_t *ids_out, doubl
   if (k < 0) return fail(PR_ERR_INVALID, "k < 0");
   if (narrow_div < 0) return fail(PR_ERR_INVALID, "narrow_div < 0");
   if (!n_out || (k > 0 && (!ids_out || !ranks_out))) return fail(PR_ERR_INVALID, "NULL argument");
+  if (b->in_done_cb) return fail(PR_ERR_STATE, kInDoneCb);
   if (!b->ready) return fail(PR_ERR_STATE, "pr_batch_get_topk_all before pr_batch_reset");
   BatchDeviceGuard dg(b->device);
   return btopk_select(&b->btopk, b->device, b->stream, b->R.as<double>(), b->V, b->width, b->stride, active_mask(b),
@@ -611,6 +732,7 @@ int step_until(pr_batch *b, int32_t max_iterations, double tol, int32_t block, i
   if (max_iterations < 0) return fail(PR_ERR_INVALID, "max_iterations < 0");
   if (!(tol >= 0.0) || std::isinf(tol)) return fail(PR_ERR_INVALID, "tol must be a finite number >= 0");
   if (block < 1) return fail(PR_ERR_INVALID, "block < 1");
+  if (b->in_done_cb) return fail(PR_ERR_STATE, kInDoneCb);
   if (!b->ready) return fail(PR_ERR_STATE, "pr_batch_step_until before pr_batch_reset");
   if (info) info[0] = info[1] = 0;
   if (max_iterations == 0) {
@@ -625,7 +747,7 @@ int step_until(pr_batch *b, int32_t max_iterations, double tol, int32_t block, i
   int32_t enq = 0;
   while (enq < max_iterations && h.mask != 0) {
     const int32_t n = std::min(block, max_iterations - enq);
-    for (int32_t i = 0; i < n; ++i, ++enq) PR_TRY(PR_BATCH_DISPATCH(launch_iteration_until, b, b->cur ^ (enq & 1), tol));
+    for (int32_t i = 0; i < n; ++i, ++enq) PR_TRY(PR_BATCH_DISPATCH(launch_iteration_until, b, b->cur ^ (enq & 1), tol, false));
     // the one read-back per block: the mask, the executed count and the per-column counts
     PR_HIP(hipMemcpyAsync(&h, b->until.p, sizeof(h), hipMemcpyDeviceToHost, b->stream));
     PR_HIP(hipStreamSynchronize(b->stream));
@@ -646,6 +768,191 @@ int check_column(const pr_batch *b, int32_t column) {
   if (!b) return fail(PR_ERR_INVALID, "NULL batch");
   if (column < 0 || column >= b->width)
     return fail(PR_ERR_INVALID, "column " + std::to_string(column) + " is outside [0, width)");
+  return PR_OK;
+}
+
+bool bad_tol(double tol) { return !(tol >= 0.0) || std::isinf(tol); }
+
+// pr_batch_step_until_any with the block size as a parameter; info (may be NULL): iterations
+// enqueued, iterations executed.
+int step_until_any(pr_batch *b, uint32_t active, int32_t max_iterations, double tol, int32_t block,
+                   int32_t *executed_out, uint32_t *converged_out, int32_t *info) {
+  if (!b) return fail(PR_ERR_INVALID, "NULL batch");
+  if (!executed_out || !converged_out) return fail(PR_ERR_INVALID, "NULL argument");
+  if (max_iterations < 0) return fail(PR_ERR_INVALID, "max_iterations < 0");
+  if (bad_tol(tol)) return fail(PR_ERR_INVALID, "tol must be a finite number >= 0");
+  if (block < 1) return fail(PR_ERR_INVALID, "block < 1");
+  if (active & ~batch_until_all(b->width)) return fail(PR_ERR_INVALID, "active names a column at or above width");
+  if (b->in_done_cb) return fail(PR_ERR_STATE, kInDoneCb);
+  if (!b->ready) return fail(PR_ERR_STATE, "pr_batch_step_until_any before pr_batch_reset");
+  *executed_out = 0;
+  *converged_out = 0;
+  if (info) info[0] = info[1] = 0;
+  if (active == 0 || max_iterations == 0) return PR_OK;
+  BatchDeviceGuard dg(b->device);
+  if (!b->until_norms) {
+    // the columns outside `active` keep their norms: from now on pr_batch_get_norms reads dcu, which
+    // so far holds nothing for them
+    const DevBuf &used = b->dc[b->iters_done > 0 ? b->cur ^ 1 : b->cur];
+    PR_HIP(hipMemcpyAsync(b->dcu.p, used.p, sizeof(double) * b->stride, hipMemcpyDeviceToDevice, b->stream));
+    b->until_norms = true;
+  }
+  BatchUntilState &h = b->h_until;
+  BatchQueueState &q = b->h_queue;
+  h = BatchUntilState{};
+  h.mask = active;
+  q = BatchQueueState{0, 0};
+  PR_HIP(hipMemcpyAsync(b->until.p, &h, sizeof(h), hipMemcpyHostToDevice, b->stream));
+  PR_HIP(hipMemcpyAsync(b->qstate.p, &q, sizeof(q), hipMemcpyHostToDevice, b->stream));
+  int32_t enq = 0;
+  while (enq < max_iterations && q.saved == 0) {
+    const int32_t n = std::min(block, max_iterations - enq);
+    for (int32_t i = 0; i < n; ++i, ++enq) PR_TRY(PR_BATCH_DISPATCH(launch_iteration_until, b, b->cur ^ (enq & 1), tol, true));
+    PR_HIP(hipMemcpyAsync(&h, b->until.p, sizeof(h), hipMemcpyDeviceToHost, b->stream));
+    PR_HIP(hipMemcpyAsync(&q, b->qstate.p, sizeof(q), hipMemcpyDeviceToHost, b->stream));
+    PR_HIP(hipStreamSynchronize(b->stream));
+  }
+  // the launches past the stopping iteration returned at entry: parity and count follow the device
+  b->cur ^= h.executed & 1;
+  b->iters_done += h.executed;
+  *executed_out = h.executed;
+  *converged_out = q.converged;
+  if (info) {
+    info[0] = enq;
+    info[1] = h.executed;
+  }
+  return PR_OK;
+}
+
+// IDs inside [0, V) and distinct, without a table of V entries: a sorted copy (tmp) shows duplicates.
+int check_ids(const pr_batch *b, int32_t n, const int32_t *ids, std::vector<int32_t> &tmp, const std::string &who) {
+  for (int32_t i = 0; i < n; ++i)
+    if (ids[i] < 0 || ids[i] >= b->V)
+      return fail(PR_ERR_INVALID, who + "[" + std::to_string(i) + "] = " + std::to_string(ids[i]) + " is outside [0, V)");
+  tmp.assign(ids, ids + n);
+  std::sort(tmp.begin(), tmp.end());
+  const auto dup = std::adjacent_find(tmp.begin(), tmp.end());
+  if (dup != tmp.end()) return fail(PR_ERR_INVALID, "vertex " + std::to_string(*dup) + " is listed twice in " + who);
+  return PR_OK;
+}
+
+// One query of pr_batch_run_queue, by the rules of pr_batch_set_teleport_sparse and pr_batch_set_exclude.
+int check_query(const pr_batch *b, const pr_batch_query &q, std::vector<int32_t> &tmp) {
+  if (q.n_seeds < 0 || q.n_exclude < 0) return fail(PR_ERR_INVALID, "n < 0");
+  if ((q.n_seeds > 0 && (!q.ids || !q.values)) || (q.n_exclude > 0 && !q.exclude)) return fail(PR_ERR_INVALID, "NULL argument");
+  if (!std::isfinite(q.rest)) return fail(PR_ERR_INVALID, "rest is not finite");
+  for (int32_t i = 0; i < q.n_seeds; ++i)
+    if (!std::isfinite(q.values[i])) return fail(PR_ERR_INVALID, "values[" + std::to_string(i) + "] is not finite");
+  PR_TRY(check_ids(b, q.n_seeds, q.ids, tmp, "ids"));
+  return check_ids(b, q.n_exclude, q.exclude, tmp, "exclude");
+}
+
+// Column j of T from a checked sparse vector, on the device: `rest` everywhere, then the n seeds.
+// n * 12 bytes cross the bus.  The caller has waited for the stream (the enqueued steps read T).
+int set_sparse_dev(pr_batch *b, int j, int32_t n, const int32_t *ids, const double *values, double rest) {
+  if (n > 0) {
+    if (b->qids.bytes < sizeof(int32_t) * (size_t)n) {
+      const size_t cap = std::max<size_t>({(size_t)n, 2 * b->qids.bytes / sizeof(int32_t), 256});
+      PR_TRY(b->qids.alloc(sizeof(int32_t) * cap));
+      PR_TRY(b->qvals.alloc(sizeof(double) * cap));
+    }
+    PR_HIP(hipMemcpyAsync(b->qids.p, ids, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, b->stream));
+    PR_HIP(hipMemcpyAsync(b->qvals.p, values, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, b->stream));
+  }
+  hipLaunchKernelGGL(k_batch_set_col, dim3(grid_for(b->V, kBatchThreads, 4096)), dim3(kBatchThreads), 0, b->stream,
+                     (int64_t)b->V, b->stride, j, (const double *)nullptr, rest, b->T.as<double>());
+  PR_HIP(hipGetLastError());
+  if (n > 0) {
+    hipLaunchKernelGGL(k_batch_scatter_col, dim3(grid_for(n, kBatchThreads, 4096)), dim3(kBatchThreads), 0, b->stream, n,
+                       b->stride, j, b->qids.as<int32_t>(), b->qvals.as<double>(), b->T.as<double>());
+    PR_HIP(hipGetLastError());
+  }
+  b->vec_mask |= 1u << j;
+  return PR_OK;
+}
+
+// Column j's exclusion set becomes the checked ids[0..n) in the host's copy of the mask; *dirty is
+// set when the device's copy has to follow (upload_exclude).  Everything that can fail comes before
+// the first change, so a failure leaves the sets as they were.
+int apply_exclude(pr_batch *b, int j, int32_t n, const int32_t *ids, bool *dirty) {
+  if (n == 0 && b->n_excl[j] == 0) return PR_OK;
+  if (!b->excl_mask.p) PR_TRY(b->excl_mask.alloc(sizeof(uint16_t) * (size_t)b->V));
+  std::vector<int32_t> mine;
+  try {
+    if (b->h_mask.empty()) b->h_mask.assign((size_t)b->V, 0);
+    mine.assign(ids, ids + n);
+  } catch (const std::bad_alloc &) {
+    return fail(PR_ERR_OOM, "host allocation failed");
+  }
+  const uint16_t bit = (uint16_t)(1u << j);
+  for (int32_t v : b->excl_ids[j]) b->h_mask[(size_t)v] &= (uint16_t)~bit;
+  for (int32_t i = 0; i < n; ++i) b->h_mask[(size_t)ids[i]] |= bit;
+  b->excl_ids[j].swap(mine);
+  b->n_excl[j] = n;
+  *dirty = true;
+  return PR_OK;
+}
+
+// The host's mask to the device, whole (2 V bytes), and waited for: the host copy may change right after.
+int upload_exclude(pr_batch *b) {
+  PR_HIP(hipMemcpyAsync(b->excl_mask.p, b->h_mask.data(), sizeof(uint16_t) * (size_t)b->V, hipMemcpyHostToDevice,
+                        b->stream));
+  PR_HIP(hipStreamSynchronize(b->stream));
+  return PR_OK;
+}
+
+int run_queue(pr_batch *b, int32_t n_queries, const pr_batch_query *queries, int32_t max_iterations, double tol,
+              const double *init_ranks, pr_batch_done_cb done, void *user) {
+  if (!b) return fail(PR_ERR_INVALID, "NULL batch");
+  if (n_queries < 0) return fail(PR_ERR_INVALID, "n_queries < 0");
+  if (n_queries > 0 && !queries) return fail(PR_ERR_INVALID, "NULL argument");
+  if (max_iterations < 1) return fail(PR_ERR_INVALID, "max_iterations < 1");
+  if (bad_tol(tol)) return fail(PR_ERR_INVALID, "tol must be a finite number >= 0");
+  if (b->in_done_cb) return fail(PR_ERR_STATE, kInDoneCb);
+  {
+    std::vector<int32_t> tmp;
+    for (int32_t q = 0; q < n_queries; ++q)
+      if (check_query(b, queries[q], tmp) != PR_OK)
+        return fail(PR_ERR_INVALID, "query " + std::to_string(q) + ": " + pr_last_error());
+  }
+  if (!b->ready) return fail(PR_ERR_STATE, "pr_batch_run_queue before pr_batch_reset");
+  if (n_queries == 0) return PR_OK;
+  BatchDeviceGuard dg(b->device);
+  PR_HIP(hipStreamSynchronize(b->stream));
+  const double *d_init = nullptr;
+  if (init_ranks && b->V > 0) {
+    if (!b->qinit.p) PR_TRY(b->qinit.alloc(sizeof(double) * (size_t)b->V));
+    PR_HIP(hipMemcpyAsync(b->qinit.p, init_ranks, sizeof(double) * (size_t)b->V, hipMemcpyHostToDevice, b->stream));
+    d_init = b->qinit.as<double>();
+  }
+  QueueSched s;
+  s.init(n_queries, b->width, max_iterations);
+  int32_t cols[kBatchMaxWidth], qs[kBatchMaxWidth];
+  QueueDone dn[kBatchMaxWidth];
+  double l1[kBatchMaxWidth];
+  while (!s.finished()) {
+    // the stream is idle here: the last call and the getters of the callbacks are synchronous
+    const int nf = s.refill(cols, qs);
+    bool mask_dirty = false;
+    for (int i = 0; i < nf; ++i) {
+      const pr_batch_query &q = queries[qs[i]];
+      PR_TRY(set_sparse_dev(b, cols[i], q.n_seeds, q.ids, q.values, q.rest));
+      PR_TRY(apply_exclude(b, cols[i], q.n_exclude, q.exclude, &mask_dirty));
+      PR_TRY(PR_BATCH_DISPATCH(launch_reset_column, b, cols[i], d_init));
+    }
+    if (mask_dirty) PR_TRY(upload_exclude(b));  // once for all the columns refilled together
+    int32_t executed = 0;
+    uint32_t converged = 0;
+    PR_TRY(step_until_any(b, s.active(), s.cap(), tol, kAnyBlock, &executed, &converged, nullptr));
+    PR_HIP(hipMemcpyAsync(l1, b->l1.p, sizeof(double) * b->stride, hipMemcpyDeviceToHost, b->stream));
+    PR_HIP(hipStreamSynchronize(b->stream));
+    const int nd = s.advance(executed, converged, dn);
+    for (int i = 0; i < nd && done; ++i) {
+      b->in_done_cb = true;
+      done(dn[i].query, dn[i].column, dn[i].iterations, dn[i].converged, l1[dn[i].column], user);
+      b->in_done_cb = false;
+    }
+  }
   return PR_OK;
 }
 
@@ -688,6 +995,7 @@ int build_batch(pr_batch *b) {
   PR_TRY(b->colbuf.alloc(sizeof(double) * V));
   PR_TRY(b->until.alloc(sizeof(BatchUntilState)));
   PR_TRY(b->dcu.alloc(sizeof(double) * S));
+  PR_TRY(b->qstate.alloc(sizeof(BatchQueueState)));
   return PR_OK;
 }
 
@@ -727,6 +1035,7 @@ int pr_batch_create(pr_graph *g, int32_t width, pr_batch **out) {
 
 int pr_batch_set_teleport(pr_batch *b, int32_t column, const double *teleport) {
   PR_TRY(pr::check_column(b, column));
+  if (b->in_done_cb) return fail(PR_ERR_STATE, pr::kInDoneCb);
   if (teleport)  // host checks first: nothing below touches the device before they pass
     for (int32_t v = 0; v < b->V; ++v)
       if (!std::isfinite(teleport[v])) return fail(PR_ERR_INVALID, "teleport[" + std::to_string(v) + "] is not finite");
@@ -740,6 +1049,7 @@ int pr_batch_set_teleport(pr_batch *b, int32_t column, const double *teleport) {
 int pr_batch_set_teleport_sparse(pr_batch *b, int32_t column, int32_t n, const int32_t *ids, const double *values,
                                  double rest) {
   PR_TRY(pr::check_column(b, column));
+  if (b->in_done_cb) return fail(PR_ERR_STATE, pr::kInDoneCb);
   if (n < 0) return fail(PR_ERR_INVALID, "n < 0");
   if (n > 0 && (!ids || !values)) return fail(PR_ERR_INVALID, "NULL argument");
   if (!std::isfinite(rest)) return fail(PR_ERR_INVALID, "rest is not finite");
@@ -763,6 +1073,7 @@ int pr_batch_set_teleport_sparse(pr_batch *b, int32_t column, int32_t n, const i
 
 int pr_batch_reset(pr_batch *b, double teleport, double damping, const double *init_ranks) {
   if (!b) return fail(PR_ERR_INVALID, "NULL batch");
+  if (b->in_done_cb) return fail(PR_ERR_STATE, pr::kInDoneCb);
   pr::BatchDeviceGuard dg(b->device);
   PR_HIP(hipStreamSynchronize(b->stream));
   b->teleport = teleport;
@@ -783,6 +1094,7 @@ int pr_batch_reset(pr_batch *b, double teleport, double damping, const double *i
 
 int pr_batch_step(pr_batch *b, int32_t iterations) {
   if (!b || iterations < 0) return fail(PR_ERR_INVALID, "NULL batch or iterations < 0");
+  if (b->in_done_cb) return fail(PR_ERR_STATE, pr::kInDoneCb);
   if (!b->ready) return fail(PR_ERR_STATE, "pr_batch_step before pr_batch_reset");
   pr::BatchDeviceGuard dg(b->device);
   if (iterations > 0) {
@@ -813,8 +1125,43 @@ int pr_batch_step_until_ex(pr_batch *b, int32_t max_iterations, double tol, int3
   return pr::step_until(b, max_iterations, tol, block, iters_out, info);
 }
 
+int pr_batch_reset_column(pr_batch *b, int32_t column, const double *init_ranks) {
+  PR_TRY(pr::check_column(b, column));
+  if (b->in_done_cb) return fail(PR_ERR_STATE, pr::kInDoneCb);
+  if (!b->ready) return fail(PR_ERR_STATE, "pr_batch_reset_column before pr_batch_reset");
+  pr::BatchDeviceGuard dg(b->device);
+  PR_HIP(hipStreamSynchronize(b->stream));  // the enqueued steps still read and write the column
+  const double *d_init = nullptr;
+  if (init_ranks && b->V > 0) {
+    PR_HIP(hipMemcpyAsync(b->colbuf.p, init_ranks, sizeof(double) * (size_t)b->V, hipMemcpyHostToDevice, b->stream));
+    d_init = b->colbuf.as<double>();
+  }
+  PR_TRY(PR_BATCH_DISPATCH(pr::launch_reset_column, b, column, d_init));
+  PR_HIP(hipStreamSynchronize(b->stream));  // init_ranks is borrowed for the call only
+  return PR_OK;
+}
+
+int pr_batch_step_until_any(pr_batch *b, uint32_t active, int32_t max_iterations, double tol, int32_t *executed_out,
+                            uint32_t *converged_out) {
+  return pr::step_until_any(b, active, max_iterations, tol, pr::kAnyBlock, executed_out, converged_out, nullptr);
+}
+
+// Internal entry point (not part of include/pagerank_hip.h): pr_batch_step_until_any with the number
+// of iterations enqueued between two read-backs as a parameter (>= 1), and info[2] = {iterations
+// enqueued, iterations executed}.
+int pr_batch_step_until_any_ex(pr_batch *b, uint32_t active, int32_t max_iterations, double tol, int32_t block,
+                               int32_t *executed_out, uint32_t *converged_out, int32_t *info) {
+  return pr::step_until_any(b, active, max_iterations, tol, block, executed_out, converged_out, info);
+}
+
+int pr_batch_run_queue(pr_batch *b, int32_t n_queries, const pr_batch_query *queries, int32_t max_iterations,
+                       double tol, const double *init_ranks, pr_batch_done_cb done, void *user) {
+  return pr::run_queue(b, n_queries, queries, max_iterations, tol, init_ranks, done, user);
+}
+
 int pr_batch_sync(pr_batch *b) {
   if (!b) return fail(PR_ERR_INVALID, "NULL batch");
+  if (b->in_done_cb) return fail(PR_ERR_STATE, pr::kInDoneCb);
   pr::BatchDeviceGuard dg(b->device);
   PR_HIP(hipStreamSynchronize(b->stream));
   return PR_OK;
@@ -868,33 +1215,26 @@ int pr_batch_get_topk(pr_batch *b, int32_t column, int32_t k, int32_t *ids_out, 
 
 int pr_batch_set_exclude(pr_batch *b, int32_t column, int32_t n, const int32_t *ids) {
   PR_TRY(pr::check_column(b, column));
+  if (b->in_done_cb) return fail(PR_ERR_STATE, pr::kInDoneCb);
   if (n < 0) return fail(PR_ERR_INVALID, "n < 0");
   if (n > 0 && !ids) return fail(PR_ERR_INVALID, "NULL argument");
   for (int32_t i = 0; i < n; ++i)
     if (ids[i] < 0 || ids[i] >= b->V)
       return fail(PR_ERR_INVALID, "ids[" + std::to_string(i) + "] = " + std::to_string(ids[i]) + " is outside [0, V)");
-  const uint16_t bit = (uint16_t)(1u << column);
   try {
     std::vector<uint8_t> seen(n > 0 ? (size_t)b->V : 0, 0);
     for (int32_t i = 0; i < n; ++i) {
       if (seen[(size_t)ids[i]]) return fail(PR_ERR_INVALID, "vertex " + std::to_string(ids[i]) + " is listed twice in ids");
       seen[(size_t)ids[i]] = 1;
     }
-    if (n > 0 && b->h_mask.empty()) b->h_mask.assign((size_t)b->V, 0);
   } catch (const std::bad_alloc &) {
     return fail(PR_ERR_OOM, "host allocation failed");
   }
   pr::BatchDeviceGuard dg(b->device);
   PR_HIP(hipStreamSynchronize(b->stream));
-  if (b->h_mask.empty()) return PR_OK;  // no set was ever stored and this one is empty
-  if (!b->excl_mask.p) PR_TRY(b->excl_mask.alloc(sizeof(uint16_t) * (size_t)b->V));
-  if (b->n_excl[column] > 0)
-    for (uint16_t &m : b->h_mask) m &= (uint16_t)~bit;
-  for (int32_t i = 0; i < n; ++i) b->h_mask[(size_t)ids[i]] |= bit;
-  b->n_excl[column] = n;
-  PR_HIP(hipMemcpyAsync(b->excl_mask.p, b->h_mask.data(), sizeof(uint16_t) * (size_t)b->V, hipMemcpyHostToDevice,
-                        b->stream));
-  PR_HIP(hipStreamSynchronize(b->stream));
+  bool dirty = false;
+  PR_TRY(pr::apply_exclude(b, column, n, ids, &dirty));  // nothing to do while no set was ever stored and this one is empty
+  if (dirty) PR_TRY(pr::upload_exclude(b));
   return PR_OK;
 }
 
@@ -913,12 +1253,14 @@ int pr_batch_topk_all_ex(pr_batch *b, int32_t k, int64_t narrow_div, int32_t *id
 // Internal: the summed HIP-event time in ns of the kernels of the last pr_batch_topk_all_ex call (-1: none).
 int pr_batch_topk_all_kernel_ns(const pr_batch *b, int64_t *ns_out) {
   if (!b || !ns_out) return fail(PR_ERR_INVALID, "NULL argument");
+  if (b->in_done_cb) return fail(PR_ERR_STATE, pr::kInDoneCb);
   *ns_out = pr::btopk_kernel_ns(b->btopk);
   return PR_OK;
 }
 
 int pr_batch_info(const pr_batch *b, int64_t *info, int32_t n_info) {
   if (!b || !info) return fail(PR_ERR_INVALID, "NULL argument");
+  if (b->in_done_cb) return fail(PR_ERR_STATE, pr::kInDoneCb);
   int64_t step_ns = -1;  // the last pr_batch_step call's iterations, HIP events; -1: none yet or still running
   float ms = 0.f;
   if (n_info > 6 && b->timed) {

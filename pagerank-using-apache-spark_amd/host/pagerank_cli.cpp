@@ -3,7 +3,7 @@
 //   pagerank <input-path> [iterations=10] [--format=edges|ccjson] [--out DIR]
 //            [--save-every-iter] [--dangling=local|none] [--device N] [--quiet] [--stats]
 //            [--resume DIR/PageRank<i>] [--devices D0,D1,...] [--top K] [--seeds FILE]
-//            [--seed-set FILE]... [--exclude-seeds] [--tol X]
+//            [--seed-set FILE]... [--exclude-seeds] [--tol X] [--seed-queue LISTFILE [--slots W]]
 //
 // Input (libpagerank_host): "src dst" edge list ("src" alone = record without links), or
 // --format=ccjson "url<TAB>json" Common Crawl metadata records (Sparky.java:61-123).  URLs are
@@ -49,6 +49,16 @@
 // writes set j to DIR/seedset<j>/PageRank<n_j - 1>.  Each listing is that of the same command without
 // --tol run for exactly n_j iterations.
 //   pagerank edges.txt 500 --seed-set alice.txt --seed-set bob.txt --top 100 --tol 1e-6
+// --seed-queue LISTFILE (needs --tol and --top; not with --seeds, --seed-set, --devices, --resume or
+// --save-every-iter; usage errors before any GPU work): LISTFILE names one seed file per line (blank
+// lines and '#' comments skipped), any number of them.  The sets are served by --slots W (1..16,
+// default min(16, sets)) batch columns through pr_batch_run_queue: a column whose set has converged
+// (or has had `iterations` iterations of its own) takes the next set at once.  No "Starting iter"
+// lines; per set, in queue order: "# seed set <q>: <FILE>", "# iterations: <n> (converged)" or
+// "(not converged)", then its --top listing (with --exclude-seeds without its own seeds) -- the lines
+// --seed-set FILE --tol X --top K prints for that file alone.  --out DIR writes set q to
+// DIR/seedset<q>/PageRank<n - 1>.
+//   pagerank edges.txt 500 --seed-queue sets.txt --tol 1e-6 --top 100 --slots 16
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -75,6 +85,8 @@ struct Options {
   int top = 0;  // --top K (0: list every URL)
   std::vector<int> devices;  // --devices: one part per entry (empty: one part on `device`)
   std::vector<std::string> seed_sets;  // --seed-set, in command-line order (empty: no batch)
+  std::string seed_queue;              // --seed-queue LISTFILE (empty: no queue)
+  int slots = 0;                       // --slots W (0: min(16, queries))
 };
 
 std::vector<int> parse_devices(const std::string &s) {
@@ -102,7 +114,10 @@ std::vector<int> parse_devices(const std::string &s) {
                "                [--exclude-seeds]  (with --seed-set and --top: a set's own seeds are left out of\n"
                "                its listing)\n"
                "                [--tol X]  (with --seed-set: every set stops once its L1 delta is <= X; iterations\n"
-               "                is the cap)\n");
+               "                is the cap)\n"
+               "                [--seed-queue LISTFILE --tol X --top K [--slots W]]  (one seed-file path per line, any\n"
+               "                number of them, served by W = 1..16 batch columns that are refilled as sets converge;\n"
+               "                not with --seeds, --seed-set, --devices, --resume or --save-every-iter)\n");
   std::exit(2);
 }
 
@@ -128,6 +143,15 @@ Options parse(int argc, char **argv) {
     else if (a.rfind("--seeds=", 0) == 0) o.seeds = a.substr(8);
     else if (a == "--seed-set" && i + 1 < argc) o.seed_sets.push_back(argv[++i]);
     else if (a.rfind("--seed-set=", 0) == 0) o.seed_sets.push_back(a.substr(11));
+    else if (a == "--seed-queue" && i + 1 < argc) o.seed_queue = argv[++i];
+    else if (a.rfind("--seed-queue=", 0) == 0) o.seed_queue = a.substr(13);
+    else if ((a == "--slots" && i + 1 < argc) || a.rfind("--slots=", 0) == 0) {
+      const std::string t = a == "--slots" ? std::string(argv[++i]) : a.substr(8);
+      if (t.empty() || t.size() > 2 || t.find_first_not_of("0123456789") != std::string::npos || std::atoi(t.c_str()) < 1 ||
+          std::atoi(t.c_str()) > 16)
+        usage("--slots takes a count W in 1..16");
+      o.slots = std::atoi(t.c_str());
+    }
     else if ((a == "--devices" && i + 1 < argc) || a.rfind("--devices=", 0) == 0) {
       o.devices = parse_devices(a == "--devices" ? std::string(argv[++i]) : a.substr(10));
       if (o.devices.empty()) usage("--devices takes a comma-separated list of device numbers");
@@ -153,6 +177,14 @@ Options parse(int argc, char **argv) {
   }
   if (o.path.empty()) usage("missing input path");
   if (o.iterations < 0) usage("iterations must be >= 0");
+  if (!o.seed_queue.empty()) {
+    if (!o.seeds.empty() || !o.seed_sets.empty() || !o.devices.empty() || !o.resume.empty() || o.save_every)
+      usage("--seed-queue does not combine with --seeds, --seed-set, --devices, --resume or --save-every-iter");
+    if (!o.has_tol || o.top == 0) usage("--seed-queue needs --tol and --top");
+    if (o.iterations < 1) usage("--seed-queue: iterations (the cap of every set) must be >= 1");
+    return o;
+  }
+  if (o.slots != 0) usage("--slots needs --seed-queue");
   if (o.exclude_seeds && (o.seed_sets.empty() || o.top == 0)) usage("--exclude-seeds needs --seed-set and --top");
   if (o.has_tol && o.seed_sets.empty()) usage("--tol needs --seed-set");
   if (!o.seed_sets.empty()) {
@@ -318,6 +350,124 @@ int run_seed_sets(const Options &o, const prh_edges *edges, const std::vector<Se
   return error;
 }
 
+// --seed-queue: the list file's seed-file paths; blank lines and '#' comments are skipped.
+bool read_seed_queue(const std::string &path, std::vector<std::string> *files) {
+  std::FILE *f = std::fopen(path.c_str(), "r");
+  if (!f) return false;
+  std::string line;
+  for (int c = 0; c != EOF;) {
+    c = std::fgetc(f);
+    if (c != EOF && c != '\n') {
+      line.push_back((char)c);
+      continue;
+    }
+    const size_t b = line.find_first_not_of(" \t\r"), e = line.find_last_not_of(" \t\r");
+    if (b != std::string::npos && line[b] != '#') files->push_back(line.substr(b, e - b + 1));
+    line.clear();
+  }
+  std::fclose(f);
+  return true;
+}
+
+// What pr_batch_run_queue's callback keeps of every set: its record and its --top pairs.
+struct QueueJob {
+  const Options *opt = nullptr;
+  const prh_edges *edges = nullptr;
+  pr_batch *b = nullptr;
+  int32_t top_k = 0;
+  std::vector<int32_t> n_it, converged, top_n, top_ids;
+  std::vector<double> top_ranks, ranks;
+  int rc = PR_OK, error = 0;
+};
+
+void on_set_done(int32_t q, int32_t column, int32_t iterations, int32_t converged, double, void *user) {
+  QueueJob *job = static_cast<QueueJob *>(user);
+  const Options &o = *job->opt;
+  job->n_it[(size_t)q] = iterations;
+  job->converged[(size_t)q] = converged;
+  if (job->rc != PR_OK) return;
+  if (!o.quiet)
+    job->rc = pr_batch_get_topk(job->b, column, job->top_k, job->top_ids.data() + (size_t)q * job->top_k,
+                                job->top_ranks.data() + (size_t)q * job->top_k, &job->top_n[(size_t)q]);
+  if (job->rc == PR_OK && !o.out.empty()) {
+    job->rc = pr_batch_get_ranks(job->b, column, job->ranks.data());
+    if (job->rc == PR_OK &&
+        prh_write_part(job->edges, (o.out + "/seedset" + std::to_string(q)).c_str(), iterations - 1, job->ranks.data()) != 0) {
+      std::fprintf(stderr, "pagerank: %s\n", prh_last_error());
+      job->error = 1;
+    }
+  }
+}
+
+// --seed-queue: the sets go through the columns of one batch (pr_batch_run_queue); a column whose
+// set is done is refilled at once.  Prints per set, in queue order, its header, its iteration count
+// and its --top listing.
+int run_seed_queue(const Options &o, const prh_edges *edges, const std::vector<std::string> &files,
+                   const std::vector<Seeds> &sets) {
+  const int32_t V = prh_n_vertices(edges);
+  const size_t Q = sets.size();
+  if (Q == 0) return 0;
+  const int32_t width = o.slots > 0 ? o.slots : (int32_t)std::min<size_t>(16, Q);
+  QueueJob job;
+  job.opt = &o;
+  job.edges = edges;
+  job.top_k = o.top < V ? o.top : V;
+  job.n_it.assign(Q, 0);
+  job.converged.assign(Q, 0);
+  job.top_n.assign(Q, 0);
+  job.top_ids.assign(Q * (size_t)job.top_k + 1, 0);
+  job.top_ranks.assign(Q * (size_t)job.top_k + 1, 0.0);
+  job.ranks.assign((size_t)V + 1, 0.0);
+  std::vector<pr_batch_query> queries(Q);
+  for (size_t q = 0; q < Q; ++q)
+    queries[q] = pr_batch_query{sets[q].n, sets[q].ids, sets[q].values.data(), 0.0, o.exclude_seeds ? sets[q].n : 0,
+                                o.exclude_seeds ? sets[q].ids : nullptr};
+  pr_graph *g = nullptr;
+  int rc = pr_graph_create(o.device, V, prh_n_edges(edges), prh_src(edges), prh_dst(edges), o.flags, &g);
+  if (rc == PR_OK) rc = pr_batch_create(g, width, &job.b);
+  if (rc == PR_OK) rc = pr_batch_reset(job.b, 0.15, 0.85, nullptr);
+  if (rc == PR_OK) rc = pr_batch_run_queue(job.b, (int32_t)Q, queries.data(), o.iterations, o.tol, nullptr, on_set_done, &job);
+  if (rc == PR_OK) rc = job.rc;
+  const std::string err = rc == PR_OK ? std::string() : std::string(pr_last_error());
+  pr_batch_destroy(job.b);  // before the graph it borrows
+  pr_graph_destroy(g);
+  if (rc != PR_OK) {
+    std::fprintf(stderr, "pagerank: --seed-queue run failed (%d): %s\n", rc, err.c_str());
+    return 1;
+  }
+  for (size_t q = 0; q < Q && !o.quiet; ++q) {
+    std::printf("# seed set %zu: %s\n", q, files[q].c_str());
+    std::printf("# iterations: %d (%s)\n", job.n_it[q], job.converged[q] ? "converged" : "not converged");
+    std::fflush(stdout);
+    if (prh_write_has_rank_ids(edges, nullptr, job.top_ids.data() + q * (size_t)job.top_k,
+                               job.top_ranks.data() + q * (size_t)job.top_k, job.top_n[q]) != 0) {
+      std::fprintf(stderr, "pagerank: %s\n", prh_last_error());
+      job.error = 1;
+    }
+    std::fflush(stdout);
+  }
+  return job.error;
+}
+
+// The seed files `paths` read and turned into teleport terms; `what` names the option in the message.
+int read_seed_files(const prh_edges *edges, const std::vector<std::string> &paths, const char *what,
+                    std::vector<Seeds> *sets) {
+  const int32_t V = prh_n_vertices(edges);
+  sets->resize(paths.size());
+  for (size_t j = 0; j < paths.size(); ++j) {
+    double *weights = nullptr;
+    Seeds &s = (*sets)[j];
+    if (prh_read_seeds(edges, paths[j].c_str(), &s.n, &s.ids, &weights) != 0) {
+      std::fprintf(stderr, "pagerank: %s %s: %s\n", what, paths[j].c_str(), prh_last_error());
+      return 2;
+    }
+    s.values.resize((size_t)s.n);
+    prh_seed_teleport(s.n, weights, 0.15, V, s.values.data());
+    prh_free_seeds(nullptr, weights);
+  }
+  return 0;
+}
+
 }  // namespace
 
 using Clock = std::chrono::steady_clock;
@@ -343,6 +493,20 @@ int main(int argc, char **argv) {
     seeds.values.resize((size_t)seeds.n);
     prh_seed_teleport(seeds.n, weights, 0.15, V, seeds.values.data());
     prh_free_seeds(nullptr, weights);
+  }
+  if (!o.seed_queue.empty()) {  // the list and every file read and checked before any graph exists
+    std::vector<std::string> files;
+    if (!read_seed_queue(o.seed_queue, &files)) {
+      std::fprintf(stderr, "pagerank: --seed-queue %s: cannot open the list file\n", o.seed_queue.c_str());
+      prh_free(edges);
+      return 2;
+    }
+    std::vector<Seeds> sets;
+    int rc = read_seed_files(edges, files, "--seed-queue", &sets);
+    if (rc == 0) rc = run_seed_queue(o, edges, files, sets);
+    for (Seeds &s : sets) prh_free_seeds(s.ids, nullptr);
+    prh_free(edges);
+    return rc;
   }
   if (!o.seed_sets.empty()) {  // every file read and checked before any graph exists
     std::vector<Seeds> sets(o.seed_sets.size());

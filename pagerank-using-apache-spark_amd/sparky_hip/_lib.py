@@ -64,6 +64,7 @@ EXPORTED = [
     "pr_batch_create", "pr_batch_set_teleport", "pr_batch_set_teleport_sparse", "pr_batch_reset", "pr_batch_step",
     "pr_batch_sync", "pr_batch_get_ranks", "pr_batch_get_norms", "pr_batch_get_topk", "pr_batch_info",
     "pr_batch_destroy", "pr_batch_set_exclude", "pr_batch_get_topk_all", "pr_batch_step_until",
+    "pr_batch_reset_column", "pr_batch_step_until_any", "pr_batch_run_queue",
 ]
 # pr_batch_info, in order
 BATCH_INFO_NAMES = ["width", "stride", "n_units", "n_long_rows", "device_bytes", "iters", "last_step_ns"]
@@ -71,6 +72,17 @@ BATCH_MAX_WIDTH = 16
 
 ITER_CB = ctypes.CFUNCTYPE(None, ctypes.c_int32, ctypes.POINTER(ctypes.c_double), ctypes.c_double,
                            ctypes.c_double, ctypes.c_double, ctypes.c_void_p)
+
+
+class BatchQuery(ctypes.Structure):
+    """pr_batch_query (include/pagerank_hip.h): one entry of pr_batch_run_queue's queue."""
+    _fields_ = [("n_seeds", ctypes.c_int32), ("ids", ctypes.c_void_p), ("values", ctypes.c_void_p),
+                ("rest", ctypes.c_double), ("n_exclude", ctypes.c_int32), ("exclude", ctypes.c_void_p)]
+
+
+# pr_batch_done_cb: query, column, iterations, converged, l1, user
+BATCH_DONE_CB = ctypes.CFUNCTYPE(None, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
+                                 ctypes.c_void_p)
 
 
 class PageRankError(RuntimeError):
@@ -82,6 +94,10 @@ class PageRankError(RuntimeError):
 
 
 _lib = None
+# Symbols that may be missing from the library PR_LIB_PATH names: a measuring tool that times an older
+# build (tools/batch_queue_bench.py --baseline-lib) lists here, before load(), what that build lacks.
+# load() then leaves them unbound; calling one still fails.  Empty in every other use.
+OPTIONAL = set()
 
 
 def load() -> ctypes.CDLL:
@@ -158,8 +174,16 @@ def load() -> ctypes.CDLL:
         "pr_batch_topk_all_kernel_ns": ([P, P], ctypes.c_int),  # HIP-event kernel time of the last _ex call
         # internal: pr_batch_step_until with the block size and the enqueued / executed iteration counts
         "pr_batch_step_until_ex": ([P, i32, dbl, i32, P, P], ctypes.c_int),
+        "pr_batch_reset_column": ([P, i32, P], ctypes.c_int),
+        "pr_batch_step_until_any": ([P, u32, i32, dbl, P, P], ctypes.c_int),
+        # the callback as a plain pointer (ctypes.cast of a BATCH_DONE_CB), so that None is NULL
+        "pr_batch_run_queue": ([P, i32, P, i32, dbl, P, P, P], ctypes.c_int),
+        # internal: pr_batch_step_until_any with the block size and the enqueued / executed counts
+        "pr_batch_step_until_any_ex": ([P, u32, i32, dbl, i32, P, P, P], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
+        if name in OPTIONAL and not hasattr(L, name):
+            continue
         fn = getattr(L, name)
         fn.argtypes = args
         fn.restype = res

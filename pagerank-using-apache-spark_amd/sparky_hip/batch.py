@@ -8,7 +8,8 @@ must be a single part that kept its canonical CSR; the batch borrows it, so clos
 (the context manager does).  ``topk_all(k)`` returns every column's top-K list from one select over
 all columns; ``set_exclude(column, ids)`` leaves vertices (a seed set, known items) out of a
 column's lists.  ``step_until(max_iterations, tol)`` stops every column at its own convergence, decided
-on the device.
+on the device.  ``run_queue(queries, max_iterations, tol)`` serves any number of seed sets through the
+columns, refilling a column (``reset_column``) as soon as its query is done (``step_until_any``).
 """
 from __future__ import annotations
 
@@ -88,6 +89,73 @@ class PageRankBatch:
         check(_lib.load().pr_batch_step_until_ex(self._h, int(max_iterations), float(tol), int(block), _ptr(iters),
                                                  _ptr(info)))
         return iters, (int(info[0]), int(info[1]))
+
+    def reset_column(self, column: int, init_ranks=None) -> None:
+        """pr_batch_reset_column: restart one column (its teleport vector as it stands, the scalar
+        teleport and damping of the last reset()); bitwise what reset() leaves in that column, the
+        other columns untouched."""
+        init = _init_array(init_ranks, self.n_vertices)
+        check(_lib.load().pr_batch_reset_column(self._h, int(column), _ptr(init)))
+
+    def step_until_any(self, active: int, max_iterations: int, tol: float):
+        """pr_batch_step_until_any: iterate the columns of the bit mask ``active`` (the others are
+        frozen) until the first iteration in which at least one of them has an L1 delta <= ``tol``, or
+        ``max_iterations`` have run.  Returns (executed, converged_mask); the mask is 0 at the cap."""
+        ex, conv = ctypes.c_int32(0), ctypes.c_uint32(0)
+        check(_lib.load().pr_batch_step_until_any(self._h, int(active), int(max_iterations), float(tol),
+                                                  ctypes.byref(ex), ctypes.byref(conv)))
+        return ex.value, conv.value
+
+    def _step_until_any_ex(self, active: int, max_iterations: int, tol: float, block: int):
+        """The internal entry point behind step_until_any() with the number of iterations enqueued
+        between two read-backs as a parameter.  Returns (executed, converged_mask, info) with
+        info = (iterations enqueued, iterations executed).  For tests and tools/batch_queue_bench.py."""
+        ex, conv, info = ctypes.c_int32(0), ctypes.c_uint32(0), np.zeros(2, np.int32)
+        check(_lib.load().pr_batch_step_until_any_ex(self._h, int(active), int(max_iterations), float(tol), int(block),
+                                                     ctypes.byref(ex), ctypes.byref(conv), _ptr(info)))
+        return ex.value, conv.value, (int(info[0]), int(info[1]))
+
+    def run_queue(self, queries, max_iterations: int, tol: float, *, k=None, init_ranks=None, on_done=None):
+        """pr_batch_run_queue: serve ``queries`` -- a sequence of (ids, values), (ids, values, rest) or
+        (ids, values, rest, exclude) -- through the batch's columns, refilling a column as soon as its
+        query has converged (L1 <= ``tol``) or has had ``max_iterations`` iterations of its own.
+        Returns one record per query, in queue order: a dict with ``iterations``, ``converged``, ``l1``,
+        ``column`` and, when ``k`` is given, ``topk`` = (ids, ranks) of the query's top-``k`` list
+        (its exclusion set left out).  ``on_done(query, column, record)`` runs as each query
+        finishes, while the column still holds its result: it may call ``self.ranks(column)``,
+        ``self.topk(column, k)`` and ``self.norms()``, nothing else on the batch."""
+        keep, arr = [], (_lib.BatchQuery * max(len(queries), 1))()
+        for n, q in enumerate(queries):
+            if not 2 <= len(q) <= 4:
+                raise ValueError("a query is (ids, values[, rest[, exclude]])")
+            i, v = _sparse_arrays(q[0], q[1])
+            x = np.zeros(0, np.int32) if len(q) < 4 or q[3] is None else np.ascontiguousarray(q[3], dtype=np.int32)
+            if x.ndim != 1:
+                raise ValueError("exclude must be a 1-D array")
+            keep.append((i, v, x))
+            arr[n] = _lib.BatchQuery(int(i.shape[0]), i.ctypes.data if i.shape[0] else None,
+                                     v.ctypes.data if v.shape[0] else None, float(q[2]) if len(q) > 2 else 0.0,
+                                     int(x.shape[0]), x.ctypes.data if x.shape[0] else None)
+        init = _init_array(init_ranks, self.n_vertices)
+        records, errors = [None] * len(queries), []
+
+        def _cb(query, column, iterations, converged, l1, _user):
+            try:
+                rec = {"iterations": int(iterations), "converged": bool(converged), "l1": float(l1), "column": int(column)}
+                if k is not None:
+                    rec["topk"] = self.topk(column, k)
+                records[query] = rec
+                if on_done is not None and not errors:
+                    on_done(int(query), int(column), rec)
+            except BaseException as e:  # never unwind through the C frames
+                errors.append(e)
+
+        cb = _lib.BATCH_DONE_CB(_cb)
+        check(_lib.load().pr_batch_run_queue(self._h, len(queries), ctypes.cast(arr, ctypes.c_void_p), int(max_iterations),
+                                             float(tol), _ptr(init), ctypes.cast(cb, ctypes.c_void_p), None))
+        if errors:
+            raise errors[0]
+        return records
 
     def sync(self) -> None:
         check(_lib.load().pr_batch_sync(self._h))

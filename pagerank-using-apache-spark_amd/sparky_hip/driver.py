@@ -3,7 +3,7 @@
 CLI: ``python -m sparky_hip <input-path> [iterations=10] [--format edges|ccjson]
 [--out DIR] [--save-every-iter] [--dangling=local|none] [--device N] [--quiet]
 [--resume DIR/PageRank<i>] [--devices D0,D1,...] [--top K] [--seeds FILE] [--seed-set FILE]...
-[--exclude-seeds] [--tol X]``
+[--exclude-seeds] [--tol X] [--seed-queue LISTFILE [--slots W]]``
 
 * input: text edge list, ``src dst`` per line; a single-token line ``src`` is a record without
   ``a`` links (Sparky.java:114-118).  Tokens (URLs) are taken verbatim and interned to dense
@@ -45,6 +45,16 @@ CLI: ``python -m sparky_hip <input-path> [iterations=10] [--form
   count; after each ``# seed set <j>: <FILE>`` line comes ``# iterations: <n_j> (converged)`` or
   ``(not converged)``; ``--out`` writes set j to ``DIR/seedset<j>/PageRank<n_j - 1>``.  Same bytes as
   the C++ CLI.
+* ``--seed-queue LISTFILE`` (needs ``--tol`` and ``--top``; not with ``--seeds``, ``--seed-set``,
+  ``--devices``, ``--resume`` or ``--save-every-iter``; usage errors before any GPU work): LISTFILE
+  names one seed file per line (blank lines and ``#`` comments skipped), any number of them.  The
+  sets are served by ``--slots W`` (1..16, default min(16, sets)) batch columns through
+  ``PageRankBatch.run_queue``: a column whose set has converged (or has had ``iterations`` iterations
+  of its own) takes the next set at once.  No ``Starting iter`` lines; per set, in queue order:
+  ``# seed set <q>: <FILE>``, ``# iterations: <n> (converged)`` or ``(not converged)``, then its
+  ``--top`` listing (with ``--exclude-seeds`` without its own seeds) -- the lines ``--seed-set FILE
+  --tol X --top K`` prints for that file alone.  ``--out DIR`` writes set q to
+  ``DIR/seedset<q>/PageRank<n - 1>``.  Same bytes as the C++ CLI.
 """
 from __future__ import annotations
 
@@ -229,6 +239,41 @@ def _run_seed_sets(edges, a, sets, top, out) -> None:
                     edges.write_has_rank(None, ranks)
 
 
+def read_seed_queue(path: str) -> List[str]:
+    """--seed-queue: the list file's seed-file paths; blank lines and ``#`` comments are skipped."""
+    with open(path, "r") as f:
+        lines = [ln.strip(" \t\r\n") for ln in f]
+    return [ln for ln in lines if ln and not ln.startswith("#")]
+
+
+def _run_seed_queue(edges, a, files, sets, top, out) -> None:
+    """--seed-queue: the sets go through the columns of one batch (PageRankBatch.run_queue).  Per
+    set, in queue order, its header, its iteration count and its --top listing."""
+    from .batch import PageRankBatch
+
+    if not sets:
+        return
+    width = a.slots or min(16, len(sets))
+    queries = [(ids, values, 0.0, ids if a.exclude_seeds else None) for ids, values in sets]
+    with PageRankGraph(edges.n_vertices, edges.src, edges.dst, device=a.device, dangling=a.dangling) as g:
+        with PageRankBatch(g, width) as b:
+            b.reset()
+
+            def on_done(q, column, rec):
+                if a.out:
+                    edges.write_part(os.path.join(a.out, f"seedset{q}"), rec["iterations"] - 1, b.ranks(column))
+
+            recs = b.run_queue(queries, a.iterations, a.tol, k=None if a.quiet else min(top, edges.n_vertices),
+                               on_done=on_done)
+    if a.quiet:
+        return
+    for q, rec in enumerate(recs):
+        out.write(f"# seed set {q}: {files[q]}\n")
+        out.write(f"# iterations: {rec['iterations']} ({'converged' if rec['converged'] else 'not converged'})\n")
+        out.flush()
+        edges.write_has_rank_ids(None, *rec["topk"])
+
+
 def main(argv=None) -> int:
     from ._host import HostEdges, HostError, seed_teleport
 
@@ -255,7 +300,15 @@ def main(argv=None) -> int:
                     help="with --seed-set and --top: a set's own seed URLs are left out of its listing")
     ap.add_argument("--tol", default=None, metavar="X",
                     help="with --seed-set: every set stops once its L1 delta is <= X; iterations is the cap")
+    ap.add_argument("--seed-queue", default=None, metavar="LISTFILE",
+                    help="a queue of seed sets (one seed-file path per line) served by --slots batch columns that are "
+                         "refilled as sets converge; needs --tol and --top")
+    ap.add_argument("--slots", default=None, metavar="W", help="with --seed-queue: the batch width, 1..16")
     a = ap.parse_args(argv)
+    if a.slots is not None:
+        if not (a.slots.isdigit() and len(a.slots) <= 2 and 1 <= int(a.slots) <= 16):
+            ap.error("--slots takes a count W in 1..16")
+        a.slots = int(a.slots)
     if a.tol is not None:
         try:
             a.tol = float(a.tol)
@@ -263,9 +316,18 @@ def main(argv=None) -> int:
             a.tol = math.nan
         if not (math.isfinite(a.tol) and a.tol >= 0.0):
             ap.error("--tol: not a finite number >= 0")
-        if not a.seed_set:
+        if not a.seed_set and a.seed_queue is None:
             ap.error("--tol needs --seed-set")
-    if a.exclude_seeds and not (a.seed_set and a.top is not None):
+    if a.seed_queue is not None:
+        if a.seeds is not None or a.seed_set or a.devices is not None or a.resume or a.save_every_iter:
+            ap.error("--seed-queue does not combine with --seeds, --seed-set, --devices, --resume or --save-every-iter")
+        if a.tol is None or a.top is None:
+            ap.error("--seed-queue needs --tol and --top")
+        if a.top >= 1 and a.iterations < 1:
+            ap.error("--seed-queue: iterations (the cap of every set) must be >= 1")
+    elif a.slots is not None:
+        ap.error("--slots needs --seed-queue")
+    if a.exclude_seeds and not ((a.seed_set or a.seed_queue is not None) and a.top is not None):
         ap.error("--exclude-seeds needs --seed-set and --top")
     if a.top is not None and a.top < 1:
         ap.error("--top takes a count K >= 1")
@@ -294,6 +356,26 @@ def main(argv=None) -> int:
             return 2
         seeds = (ids, seed_teleport(weights, edges.n_vertices))  # the native expression: the C++ CLI's bits
     out = sys.stdout
+    if a.seed_queue is not None:  # the list and every file read and checked before any graph exists
+        try:
+            files = read_seed_queue(a.seed_queue)
+        except OSError:
+            sys.stderr.write(f"sparky_hip: --seed-queue {a.seed_queue}: cannot open the list file\n")
+            edges.close()
+            return 2
+        sets = []
+        for path in files:
+            try:
+                ids, weights = edges.read_seeds(path)
+            except HostError as e:
+                sys.stderr.write(f"sparky_hip: --seed-queue {path}: {e}\n")
+                edges.close()
+                return 2
+            sets.append((ids, seed_teleport(weights, edges.n_vertices)))
+        _run_seed_queue(edges, a, files, sets, top, out)
+        out.flush()
+        edges.close()
+        return 0
     if a.seed_set:  # every file read and checked before any graph exists
         sets = []
         for path in a.seed_set:

@@ -405,6 +405,44 @@ typedef void (*pr_batch_done_cb)(int32_t query, int32_t column, int32_t iteratio
 int pr_batch_run_queue(pr_batch *b, int32_t n_queries, const pr_batch_query *queries,
                        int32_t max_iterations, double tol, const double *init_ranks,
                        pr_batch_done_cb done, void *user);
+/* Where a column's dangling mass goes.  PR_BATCH_DANGLING_UNIFORM (the default) is the iteration
+ * above, bit for bit: every vertex receives dc_j / N.  PR_BATCH_DANGLING_TELEPORT returns the mass
+ * along the column's teleport vector, as textbook personalised PageRank does: with
+ * ts_j = sum_v t_j[v],
+ *     q_j   = dc_j / ts_j                               (one rounded divide)
+ *     r'[v] = t_j[v] + damping * (S_j[v] + q_j * t_j[v])
+ * every operation rounded on its own (no contraction), S_j and dc_j exactly as in uniform mode.
+ * With t = (0.15 N) p for a probability vector p the term is dc_j * p[v]: the mass goes back to the
+ * seeds, and a vertex the seeds cannot reach keeps a rank of 0.  Everything else stays Sparky's:
+ * unnormalised ranks, S = r_old for rows without in-links, the leak of no-link keys.
+ * Fallback, per column: a column without a vector, a padding column, and a column whose ts_j is
+ * exactly 0 or not finite use the uniform dc_j / N, bit for bit; a negative ts_j is allowed.  On a
+ * PR_DANGLING_NONE graph dc is 0 and the mode has no effect (the uniform kernels run).
+ * ts_j is formed on the device from the column of T in a fixed order that depends on V and the
+ * stride only (pr_batch_reset_column's traversal and summation): a sparse set and the equal dense
+ * vector give the same bits, as does the same vector in any column of a batch of the same stride,
+ * and two runs agree.  It is brought up to date, for every column whose vector changed (set, clear,
+ * queue refill, or the mode switched on), before the next teleport-mode iteration is enqueued and
+ * before pr_batch_get_teleport_sums returns; with the mode off no existing call launches anything
+ * for it.  The mode holds for pr_batch_step, pr_batch_step_until, pr_batch_step_until_any and
+ * pr_batch_run_queue, and every statement made for them above stays true with "in the same mode"
+ * added (a column's bits do not depend on its position or neighbours, step_until leaves column j
+ * where step(iters_j) leaves it, a frozen column keeps its bits, a queue query equals a fresh batch
+ * of the same width in the same mode).  pr_batch_reset, pr_batch_reset_column, the norms (dc used,
+ * L1) and the top-K queries are the same in both modes.
+ * pr_batch_set_dangling waits for the enqueued steps, is valid any time after create, survives
+ * pr_batch_reset and takes effect from the next iteration enqueued.  The width doubles of ts are
+ * allocated with the first use of the mode or of the getter and counted in pr_batch_info's device
+ * bytes from then on.  The mode is the batch's: there is no per-column or per-query mode, and the
+ * engine's own iteration (pr_set_teleport, pr_step, pr_group_*) keeps the uniform term.
+ * A NULL batch or output, a mode other than the two constants: PR_ERR_INVALID, nothing changed;
+ * inside pr_batch_run_queue's callback: PR_ERR_STATE. */
+#define PR_BATCH_DANGLING_UNIFORM 0
+#define PR_BATCH_DANGLING_TELEPORT 1
+int pr_batch_set_dangling(pr_batch *b, int32_t mode);
+int pr_batch_get_dangling(const pr_batch *b, int32_t *mode_out);
+/* ts_j of every column: width doubles; 0.0 for a column without a vector.  Synchronous. */
+int pr_batch_get_teleport_sums(pr_batch *b, double *sums_out);
 int pr_batch_sync(pr_batch *b);
 /* Column `column`: V doubles in original-ID order.  Waits for the enqueued steps. */
 int pr_batch_get_ranks(pr_batch *b, int32_t column, double *ranks_out);

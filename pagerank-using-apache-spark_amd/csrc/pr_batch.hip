@@ -38,6 +38,12 @@
 // k_batch_decide_any in k_batch_decide's place, which empties the mask after the first iteration in
 // which a column converged.
 //
+// pr_batch_set_dangling(PR_BATCH_DANGLING_TELEPORT) replaces the unit and long-row kernels of all of
+// the above by k_batch_units_td / k_batch_long_td, which return column j's dangling mass along its
+// teleport vector (q_j * t[p], q_j = dc_j / ts_j) where ts_j -- the vector's sum, formed by
+// k_batch_tsum_col in k_batch_reset_col's order whenever a vector changed -- is finite and not 0, and
+// add the uniform dc_j / N otherwise (pr_batch_dangling.h).  In the default mode none of these runs.
+//
 // The batch only reads the graph's canon_* buffers; it launches none of the graph's kernels and
 // owns its stream and all its state.
 #include <algorithm>
@@ -47,6 +53,7 @@
 #include <vector>
 
 #include "pr_batch.h"
+#include "pr_batch_dangling.h"
 #include "pr_batch_topk.h"
 #include "pr_batch_queue.h"
 #include "pr_batch_until.h"
@@ -88,6 +95,12 @@ struct pr_batch {
   std::vector<int32_t> excl_ids[pr::kBatchMaxWidth];  // the IDs behind n_excl, to clear a set in O(n)
   bool in_done_cb = false;  // pr_batch_run_queue is inside its callback: only the three getters run
   uint32_t vec_mask = 0;  // columns with a teleport vector set
+  // pr_batch_set_dangling: the mode; ts (stride doubles, allocated with the first use of teleport mode
+  // or of pr_batch_get_teleport_sums) holds the sums of the columns' teleport vectors, 0 without one;
+  // bit j of ts_dirty: column j's vector changed since ts[j] was formed
+  int32_t dangling_mode = PR_BATCH_DANGLING_UNIFORM;
+  pr::DevBuf ts;
+  uint32_t ts_dirty = 0;
   double teleport = 0.15, damping = 0.85;
   int cur = 0;
   int64_t iters_done = 0;
@@ -100,7 +113,7 @@ struct pr_batch {
     return units.bytes + long_row.bytes + long_p0.bytes + chunk_part.bytes + R.bytes + T.bytes + C[0].bytes +
            C[1].bytes + dc[0].bytes + dc[1].bytes + l1.bytes + part.bytes + colbuf.bytes + pr::topk_state_bytes(topk) +
            until.bytes + dcu.bytes + excl_mask.bytes + excl_oid.bytes + pr::btopk_state_bytes(btopk) + qstate.bytes +
-           qids.bytes + qvals.bytes + qinit.bytes;
+           qids.bytes + qvals.bytes + qinit.bytes + ts.bytes;
   }
 };
 
@@ -443,6 +456,161 @@ __global__ __launch_bounds__(kWave) void k_batch_decide_any(BatchUntilState *__r
   us->mask = batch_any_decide(m, l1, tol, width, qs);
 }
 
+// ---- PR_BATCH_DANGLING_TELEPORT's siblings of the unit and long-row kernels --------------------
+// Again the same statements in the same order, kept apart so that the kernels above compile exactly
+// as before.  UNTIL selects the masked form (k_batch_units_until / k_batch_long_until's extras), so
+// the two templates stand for four kernels; the finalize and decide kernels are shared with uniform
+// mode, which they do not see.  ts[0..S) holds the sums of the columns' teleport vectors
+// (k_batch_tsum_col; 0 for a column without one and for padding).  A lane picks, once at entry and
+// as a select, its factor q_j = dc_j / ts_j or the uniform term dc_j / N (pr_batch_dangling.h);
+// an element then adds q_j * t[p] or that term.  Nothing that shuffles or waits depends on the pick.
+__device__ __forceinline__ void update_elem_td(const BatchArgs &a, int64_t v, int64_t p, double Sv, double rold,
+                                               uint32_t f, bool use, double qf, bool act, double &dcp, double &l1p) {
+  if (act) {
+    const double tp = a.t[p];
+    const double rn = batch_affine(Sv, use ? batch_dangling_term(qf, tp) : qf, tp, a.damping);
+    a.r[p] = rn;
+    const int32_t d = a.deg[v];
+    if (d > 0) a.cout[p] = __ddiv_rn(rn, (double)d);
+    else if ((f & PR_VF_SINK) && !a.dangling_none) dcp = __dadd_rn(dcp, rn);
+    l1p = __dadd_rn(l1p, fabs(rn - rold));
+  } else if (a.deg[v] > 0) {
+    a.cout[p] = a.cin[p];
+  }
+}
+
+template <int S, bool UNTIL>
+__global__ __launch_bounds__(kWave) void k_batch_units_td(BatchArgs a, const double *__restrict__ ts,
+                                                          const BatchUntilState *__restrict__ us) {
+  constexpr int G = kWave / S;
+  __shared__ double sS[kBatchUnitRows * S];
+  uint32_t m = 0xffffffffu;
+  if (UNTIL) {
+    m = us->mask;  // one word, the same for every lane: a uniform exit
+    if (m == 0) return;
+  }
+  const int lane = threadIdx.x, g = lane / S, j = lane % S;
+  const bool act = (m >> j) & 1u;
+  const double tsj = ts[j];
+  const bool use = batch_dangling_uses_teleport(tsj);
+  const double qf = batch_dangling_factor(use, a.dc[j], tsj, a.n_vertices);
+  double dcp = 0.0, l1p = 0.0;
+  for (int64_t u = blockIdx.x; u < a.n_units; u += gridDim.x) {
+    const BatchUnit un = a.units[u];
+    if (un.rows < 0) {  // CHUNK
+      const double acc = row_sum<S>(a.col, a.cin, un.e0, un.e0 + un.n, g, j);
+      if (lane < S) a.chunk_part[(int64_t)un.slot * S + j] = acc;
+      continue;
+    }
+    const int rows = un.rows;
+    const long long rp_l = (long long)a.rowptr[(int64_t)un.row0 + (lane < rows ? lane : rows)];
+    const int64_t uend = un.e0 + un.n;
+    for (int k0 = 0; k0 < rows; k0 += G) {  // short rows
+      const int k = k0 + g;
+      const int ks = k < rows ? k : 0;
+      const int64_t b = __shfl(rp_l, ks, kWave);
+      const int64_t e1 = __shfl(rp_l, ks + 1 < kWave ? ks + 1 : kWave - 1, kWave);
+      const int64_t deg = k < rows ? (ks + 1 < rows ? e1 : uend) - b : 0;
+      if (deg > 0 && deg <= kBatchShortRow) {
+        int32_t c[kBatchShortRow];
+        double x[kBatchShortRow];
+#pragma unroll
+        for (int q = 0; q < kBatchShortRow; ++q) c[q] = q < deg ? a.col[b + q] : 0;
+#pragma unroll
+        for (int q = 0; q < kBatchShortRow; ++q) x[q] = q < deg ? a.cin[(int64_t)c[q] * S + j] : 0.0;
+        double acc = 0.0;
+#pragma unroll
+        for (int q = 0; q < kBatchShortRow; ++q)
+          if (q < deg) acc = __dadd_rn(acc, x[q]);
+        sS[k * S + j] = acc;
+      }
+    }
+    for (int k = 0; k < rows; ++k) {  // longer rows
+      const int64_t b = __shfl(rp_l, k, kWave);
+      const int64_t e = k + 1 < rows ? (int64_t)__shfl(rp_l, k + 1, kWave) : uend;
+      if (e - b <= kBatchShortRow) continue;
+      const double acc = row_sum<S>(a.col, a.cin, b, e, g, j);
+      if (lane < S) sS[k * S + j] = acc;
+    }
+    __syncthreads();
+    const int total = rows * S;
+    for (int idx = lane; idx < total; idx += kWave) {
+      const int64_t v = (int64_t)un.row0 + idx / S, p = v * S + j;
+      const uint32_t f = a.vflags[v];
+      const double rold = a.r[p];
+      update_elem_td(a, v, p, (f & PR_VF_INDEG0) ? rold : sS[idx], rold, f, use, qf, act, dcp, l1p);
+    }
+    __syncthreads();
+  }
+  dcp = group_sum<S>(dcp);
+  l1p = group_sum<S>(l1p);
+  if (lane < S) {
+    a.part[((int64_t)blockIdx.x * 2) * S + j] = dcp;
+    a.part[((int64_t)blockIdx.x * 2 + 1) * S + j] = l1p;
+  }
+}
+
+template <int S, bool UNTIL>
+__global__ __launch_bounds__(kBatchThreads) void k_batch_long_td(BatchArgs a, const int32_t *__restrict__ long_row,
+                                                                 const int32_t *__restrict__ long_p0, int64_t n_long,
+                                                                 int64_t part_block0, const double *__restrict__ ts,
+                                                                 const BatchUntilState *__restrict__ us) {
+  uint32_t m = 0xffffffffu;
+  if (UNTIL) {
+    m = us->mask;
+    if (m == 0) return;  // uniform, and before the barrier of block_col_part
+  }
+  const int64_t idx = (int64_t)blockIdx.x * kBatchThreads + threadIdx.x;
+  const int64_t q = idx / S;
+  const int j = threadIdx.x % S;
+  double dcp = 0.0, l1p = 0.0;
+  if (q < n_long) {
+    const int32_t p0 = long_p0[q], p1 = long_p0[q + 1];
+    double acc = 0.0;
+    for (int32_t k = p0; k < p1; ++k) acc = __dadd_rn(acc, a.chunk_part[(int64_t)k * S + j]);
+    const int64_t v = long_row[q], p = v * S + j;
+    const double tsj = ts[j];
+    const bool use = batch_dangling_uses_teleport(tsj);
+    update_elem_td(a, v, p, acc, a.r[p], a.vflags[v], use, batch_dangling_factor(use, a.dc[j], tsj, a.n_vertices),
+                   (m >> j) & 1u, dcp, l1p);
+  }
+  block_col_part<S>(dcp, l1p, a.part, part_block0 + blockIdx.x);
+}
+
+// The sum of column j of T for teleport mode, in k_batch_reset_col's traversal (launched with
+// k_batch_reset's grid): the threads with threadIdx.x % S == j add the elements they visit there, in
+// that order; the workgroup's sum of its threads' partials, in thread order, goes to
+// part1[blockIdx.x].  The order depends on V and S only, not on j: thread S * m + j of workgroup b
+// visits the vertices thread S * m of it would.  part1 is the part scratch: every launch that uses
+// it is on the batch's stream, so they take turns.
+template <int S>
+__global__ __launch_bounds__(kBatchThreads) void k_batch_tsum_col(int64_t V, int j, const double *__restrict__ t,
+                                                                  double *__restrict__ part1) {
+  __shared__ double sh[kBatchThreads];
+  const int tx = threadIdx.x;
+  double acc = 0.0;
+  if (tx % S == j)
+    for (int64_t p = (int64_t)blockIdx.x * kBatchThreads + tx; p < V * S; p += (int64_t)gridDim.x * kBatchThreads)
+      acc = __dadd_rn(acc, t[p]);
+  sh[tx] = acc;
+  __syncthreads();
+  if (tx == 0) {
+    double x = 0.0;
+    for (int k = j; k < kBatchThreads; k += S) x = __dadd_rn(x, sh[k]);
+    part1[blockIdx.x] = x;
+  }
+}
+
+// k_batch_finalize_col's strided sums and block_sum over part1, into ts[j].
+__global__ __launch_bounds__(kBatchThreads) void k_batch_tsum_finalize(const double *__restrict__ part1, int64_t n_blocks,
+                                                                       int j, double *__restrict__ ts) {
+  __shared__ double red[kBatchThreads / kWave];
+  double acc = 0.0;
+  for (int64_t b = threadIdx.x; b < n_blocks; b += kBatchThreads) acc = __dadd_rn(acc, part1[b]);
+  acc = block_sum<kBatchThreads>(acc, red);
+  if (threadIdx.x == 0) ts[j] = acc;
+}
+
 // Ranks to init (or 1.0) in every column, the scalar teleport into the columns without a vector,
 // the contributions of those ranks, zeros into the padding columns; per-workgroup dangling partials.
 // gridDim.x * kBatchThreads is a multiple of S, so a thread stays in column threadIdx.x % S.
@@ -591,9 +759,66 @@ BatchArgs batch_args(const pr_batch *b) {
   return a;
 }
 
+#define PR_BATCH_DISPATCH(fn, b, ...)                                    \
+  ((b)->stride == 1   ? fn<1>(b, ##__VA_ARGS__)                          \
+   : (b)->stride == 2 ? fn<2>(b, ##__VA_ARGS__)                          \
+   : (b)->stride == 4 ? fn<4>(b, ##__VA_ARGS__)                          \
+   : (b)->stride == 8 ? fn<8>(b, ##__VA_ARGS__)                          \
+                      : fn<16>(b, ##__VA_ARGS__))
+
+// Whether the iterations enqueued now run the teleport-mode kernels.  On a PR_DANGLING_NONE graph
+// dc is 0 and both terms vanish: the uniform kernels run.
+bool teleport_mode(const pr_batch *b) { return b->dangling_mode == PR_BATCH_DANGLING_TELEPORT && !b->dangling_none; }
+
+// Enqueues the sum of column j of T into ts[j] (k_batch_reset_col's grid and order).
+template <int S>
+int launch_tsum_column(pr_batch *b, int j) {
+  const unsigned grid = grid_for((int64_t)b->V * S, kBatchThreads, kBatchGridMax);  // k_batch_reset's
+  hipLaunchKernelGGL(k_batch_tsum_col<S>, dim3(grid), dim3(kBatchThreads), 0, b->stream, (int64_t)b->V, j,
+                     b->T.as<double>(), b->part.as<double>());
+  PR_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_batch_tsum_finalize, dim3(1), dim3(kBatchThreads), 0, b->stream, b->part.as<double>(),
+                     (int64_t)grid, j, b->ts.as<double>());
+  PR_HIP(hipGetLastError());
+  return PR_OK;
+}
+
+// Brings ts up to date on the batch's stream: the sum of every column whose vector changed, 0.0 for
+// a column whose vector was cleared.  Allocates ts (zeros: padding columns stay 0) on first use.
+// Everything that touches the part scratch or T is on the same stream, so no wait is needed.
+int ensure_ts(pr_batch *b) {
+  if (!b->ts.p) {
+    PR_TRY(b->ts.alloc(sizeof(double) * b->stride));
+    PR_HIP(hipMemsetAsync(b->ts.p, 0, sizeof(double) * b->stride, b->stream));
+    b->ts_dirty = b->vec_mask;
+  }
+  for (int j = 0; j < b->width && b->ts_dirty; ++j) {
+    if (!((b->ts_dirty >> j) & 1u)) continue;
+    if ((b->vec_mask >> j) & 1u) PR_TRY(PR_BATCH_DISPATCH(launch_tsum_column, b, j));
+    else PR_HIP(hipMemsetAsync(b->ts.as<double>() + j, 0, sizeof(double), b->stream));
+    b->ts_dirty &= ~(1u << j);
+  }
+  return PR_OK;
+}
+
 template <int S>
 int launch_iteration(pr_batch *b) {
   const BatchArgs a = batch_args(b);
+  if (teleport_mode(b)) {  // the caller has brought ts up to date
+    hipLaunchKernelGGL((k_batch_units_td<S, false>), dim3(b->ugrid), dim3(kWave), 0, b->stream, a, b->ts.as<double>(),
+                       (const BatchUntilState *)nullptr);
+    PR_HIP(hipGetLastError());
+    if (b->n_long > 0) {
+      hipLaunchKernelGGL((k_batch_long_td<S, false>), dim3(b->lgrid), dim3(kBatchThreads), 0, b->stream, a,
+                         b->long_row.as<int32_t>(), b->long_p0.as<int32_t>(), b->n_long, (int64_t)b->ugrid,
+                         b->ts.as<double>(), (const BatchUntilState *)nullptr);
+      PR_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_batch_finalize, dim3(2 * S), dim3(kBatchThreads), 0, b->stream, b->part.as<double>(),
+                       (int64_t)b->ugrid + b->lgrid, S, b->dc[b->cur ^ 1].as<double>(), b->l1.as<double>());
+    PR_HIP(hipGetLastError());
+    return PR_OK;
+  }
   hipLaunchKernelGGL(k_batch_units<S>, dim3(b->ugrid), dim3(kWave), 0, b->stream, a);
   PR_HIP(hipGetLastError());
   if (b->n_long > 0) {
@@ -616,12 +841,23 @@ int launch_iteration_until(pr_batch *b, int cur, double tol, bool any) {
   a.cout = b->C[cur ^ 1].as<double>();
   a.dc = b->dc[cur].as<double>();
   const BatchUntilState *us = b->until.as<BatchUntilState>();
-  hipLaunchKernelGGL(k_batch_units_until<S>, dim3(b->ugrid), dim3(kWave), 0, b->stream, a, us);
-  PR_HIP(hipGetLastError());
-  if (b->n_long > 0) {
-    hipLaunchKernelGGL(k_batch_long_until<S>, dim3(b->lgrid), dim3(kBatchThreads), 0, b->stream, a,
-                       b->long_row.as<int32_t>(), b->long_p0.as<int32_t>(), b->n_long, (int64_t)b->ugrid, us);
+  if (teleport_mode(b)) {  // the caller has brought ts up to date
+    hipLaunchKernelGGL((k_batch_units_td<S, true>), dim3(b->ugrid), dim3(kWave), 0, b->stream, a, b->ts.as<double>(), us);
     PR_HIP(hipGetLastError());
+    if (b->n_long > 0) {
+      hipLaunchKernelGGL((k_batch_long_td<S, true>), dim3(b->lgrid), dim3(kBatchThreads), 0, b->stream, a,
+                         b->long_row.as<int32_t>(), b->long_p0.as<int32_t>(), b->n_long, (int64_t)b->ugrid,
+                         b->ts.as<double>(), us);
+      PR_HIP(hipGetLastError());
+    }
+  } else {
+    hipLaunchKernelGGL(k_batch_units_until<S>, dim3(b->ugrid), dim3(kWave), 0, b->stream, a, us);
+    PR_HIP(hipGetLastError());
+    if (b->n_long > 0) {
+      hipLaunchKernelGGL(k_batch_long_until<S>, dim3(b->lgrid), dim3(kBatchThreads), 0, b->stream, a,
+                         b->long_row.as<int32_t>(), b->long_p0.as<int32_t>(), b->n_long, (int64_t)b->ugrid, us);
+      PR_HIP(hipGetLastError());
+    }
   }
   hipLaunchKernelGGL(k_batch_finalize_until, dim3(2 * S), dim3(kBatchThreads), 0, b->stream, b->part.as<double>(),
                      (int64_t)b->ugrid + b->lgrid, S, b->dc[cur].as<double>(), b->dc[cur ^ 1].as<double>(),
@@ -668,13 +904,6 @@ int launch_reset(pr_batch *b, const double *d_init) {
   PR_HIP(hipGetLastError());
   return PR_OK;
 }
-
-#define PR_BATCH_DISPATCH(fn, b, ...)                                    \
-  ((b)->stride == 1   ? fn<1>(b, ##__VA_ARGS__)                          \
-   : (b)->stride == 2 ? fn<2>(b, ##__VA_ARGS__)                          \
-   : (b)->stride == 4 ? fn<4>(b, ##__VA_ARGS__)                          \
-   : (b)->stride == 8 ? fn<8>(b, ##__VA_ARGS__)                          \
-                      : fn<16>(b, ##__VA_ARGS__))
 
 // Column j of T: V doubles from the host (through colbuf), or `value` everywhere (host == nullptr).
 int upload_column(pr_batch *b, int j, const double *host, double value) {
@@ -740,6 +969,7 @@ int step_until(pr_batch *b, int32_t max_iterations, double tol, int32_t block, i
     return PR_OK;
   }
   BatchDeviceGuard dg(b->device);
+  if (teleport_mode(b)) PR_TRY(ensure_ts(b));
   BatchUntilState &h = b->h_until;
   h = BatchUntilState{};
   h.mask = batch_until_all(b->width);
@@ -790,6 +1020,7 @@ int step_until_any(pr_batch *b, uint32_t active, int32_t max_iterations, double 
   if (info) info[0] = info[1] = 0;
   if (active == 0 || max_iterations == 0) return PR_OK;
   BatchDeviceGuard dg(b->device);
+  if (teleport_mode(b)) PR_TRY(ensure_ts(b));
   if (!b->until_norms) {
     // the columns outside `active` keep their norms: from now on pr_batch_get_norms reads dcu, which
     // so far holds nothing for them
@@ -868,6 +1099,7 @@ int set_sparse_dev(pr_batch *b, int j, int32_t n, const int32_t *ids, const doub
     PR_HIP(hipGetLastError());
   }
   b->vec_mask |= 1u << j;
+  b->ts_dirty |= 1u << j;
   return PR_OK;
 }
 
@@ -1043,6 +1275,7 @@ int pr_batch_set_teleport(pr_batch *b, int32_t column, const double *teleport) {
   PR_TRY(pr::upload_column(b, column, teleport, b->teleport));
   if (teleport) b->vec_mask |= 1u << column;
   else b->vec_mask &= ~(1u << column);
+  b->ts_dirty |= 1u << column;
   return PR_OK;
 }
 
@@ -1068,6 +1301,7 @@ int pr_batch_set_teleport_sparse(pr_batch *b, int32_t column, int32_t n, const i
   pr::BatchDeviceGuard dg(b->device);
   PR_TRY(pr::upload_column(b, column, dense.data(), 0.0));
   b->vec_mask |= 1u << column;
+  b->ts_dirty |= 1u << column;
   return PR_OK;
 }
 
@@ -1097,6 +1331,7 @@ int pr_batch_step(pr_batch *b, int32_t iterations) {
   if (b->in_done_cb) return fail(PR_ERR_STATE, pr::kInDoneCb);
   if (!b->ready) return fail(PR_ERR_STATE, "pr_batch_step before pr_batch_reset");
   pr::BatchDeviceGuard dg(b->device);
+  if (iterations > 0 && pr::teleport_mode(b)) PR_TRY(pr::ensure_ts(b));
   if (iterations > 0) {
     PR_HIP(hipEventRecord(b->ev0, b->stream));
     b->until_norms = false;  // every column advances: the last iteration's dc is dc[cur ^ 1] again
@@ -1159,6 +1394,36 @@ int pr_batch_run_queue(pr_batch *b, int32_t n_queries, const pr_batch_query *que
   return pr::run_queue(b, n_queries, queries, max_iterations, tol, init_ranks, done, user);
 }
 
+int pr_batch_set_dangling(pr_batch *b, int32_t mode) {
+  if (!b) return fail(PR_ERR_INVALID, "NULL batch");
+  if (mode != PR_BATCH_DANGLING_UNIFORM && mode != PR_BATCH_DANGLING_TELEPORT)
+    return fail(PR_ERR_INVALID, "mode must be PR_BATCH_DANGLING_UNIFORM or PR_BATCH_DANGLING_TELEPORT");
+  if (b->in_done_cb) return fail(PR_ERR_STATE, pr::kInDoneCb);
+  pr::BatchDeviceGuard dg(b->device);
+  PR_HIP(hipStreamSynchronize(b->stream));
+  b->dangling_mode = mode;  // ts follows before the next teleport-mode iteration is enqueued (ensure_ts)
+  return PR_OK;
+}
+
+int pr_batch_get_dangling(const pr_batch *b, int32_t *mode_out) {
+  if (!b || !mode_out) return fail(PR_ERR_INVALID, "NULL argument");
+  if (b->in_done_cb) return fail(PR_ERR_STATE, pr::kInDoneCb);
+  *mode_out = b->dangling_mode;
+  return PR_OK;
+}
+
+int pr_batch_get_teleport_sums(pr_batch *b, double *sums_out) {
+  if (!b || !sums_out) return fail(PR_ERR_INVALID, "NULL argument");
+  if (b->in_done_cb) return fail(PR_ERR_STATE, pr::kInDoneCb);
+  pr::BatchDeviceGuard dg(b->device);
+  PR_TRY(pr::ensure_ts(b));
+  double ts[pr::kBatchMaxWidth];
+  PR_HIP(hipMemcpyAsync(ts, b->ts.p, sizeof(double) * b->stride, hipMemcpyDeviceToHost, b->stream));
+  PR_HIP(hipStreamSynchronize(b->stream));
+  std::copy(ts, ts + b->width, sums_out);
+  return PR_OK;
+}
+
 int pr_batch_sync(pr_batch *b) {
   if (!b) return fail(PR_ERR_INVALID, "NULL batch");
   if (b->in_done_cb) return fail(PR_ERR_STATE, pr::kInDoneCb);
@@ -1171,6 +1436,21 @@ int pr_batch_get_ranks(pr_batch *b, int32_t column, double *ranks_out) {
   PR_TRY(pr::check_column(b, column));
   if (!ranks_out) return fail(PR_ERR_INVALID, "NULL argument");
   if (!b->ready) return fail(PR_ERR_STATE, "pr_batch_get_ranks before pr_batch_reset");
+  pr::BatchDeviceGuard dg(b->device);
+  PR_TRY(pr::extract_column(b, column));
+  if (b->V > 0)
+    PR_HIP(hipMemcpyAsync(ranks_out, b->colbuf.p, sizeof(double) * (size_t)b->V, hipMemcpyDeviceToHost, b->stream));
+  PR_HIP(hipStreamSynchronize(b->stream));
+  return PR_OK;
+}
+
+// Internal entry point (not part of include/pagerank_hip.h): pr_batch_get_ranks for any column of the
+// layout, [0, stride), so that tests can show that the padding columns hold zeros.
+int pr_batch_get_ranks_ex(pr_batch *b, int32_t column, double *ranks_out) {
+  if (!b || !ranks_out) return fail(PR_ERR_INVALID, "NULL argument");
+  if (column < 0 || column >= b->stride) return fail(PR_ERR_INVALID, "column is outside [0, stride)");
+  if (b->in_done_cb) return fail(PR_ERR_STATE, pr::kInDoneCb);
+  if (!b->ready) return fail(PR_ERR_STATE, "pr_batch_get_ranks_ex before pr_batch_reset");
   pr::BatchDeviceGuard dg(b->device);
   PR_TRY(pr::extract_column(b, column));
   if (b->V > 0)

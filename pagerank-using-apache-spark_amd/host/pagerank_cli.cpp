@@ -59,6 +59,14 @@
 // --seed-set FILE --tol X --top K prints for that file alone.  --out DIR writes set q to
 // DIR/seedset<q>/PageRank<n - 1>.
 //   pagerank edges.txt 500 --seed-queue sets.txt --tol 1e-6 --top 100 --slots 16
+// --dangling-to-seeds (needs --seed-set or --seed-queue, else a usage error before any GPU work): every
+// set's dangling mass returns to that set's own seeds, in proportion to their weights
+// (pr_batch_set_dangling, PR_BATCH_DANGLING_TELEPORT), instead of being spread over all URLs: a URL the
+// seeds cannot reach keeps rank 0.  A set whose teleport terms sum to 0 or overflow keeps the uniform term; with
+// --dangling=none there is no dangling mass and the option changes nothing.  The mode is the whole
+// run's, not a set's; --seeds (the engine's own iteration) keeps the uniform term.  Output format
+// unchanged.
+//   pagerank edges.txt 20 --seed-set alice.txt --seed-set bob.txt --top 100 --dangling-to-seeds
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -78,6 +86,7 @@ struct Options {
   int format = PRH_FORMAT_EDGES;
   bool save_every = false, quiet = false, stats = false;
   bool exclude_seeds = false;  // --exclude-seeds
+  bool dangling_to_seeds = false;  // --dangling-to-seeds
   bool has_tol = false;        // --tol X: `iterations` is the cap
   double tol = 0.0;
   uint32_t flags = PR_DANGLING_LOCAL;
@@ -117,7 +126,10 @@ std::vector<int> parse_devices(const std::string &s) {
                "                is the cap)\n"
                "                [--seed-queue LISTFILE --tol X --top K [--slots W]]  (one seed-file path per line, any\n"
                "                number of them, served by W = 1..16 batch columns that are refilled as sets converge;\n"
-               "                not with --seeds, --seed-set, --devices, --resume or --save-every-iter)\n");
+               "                not with --seeds, --seed-set, --devices, --resume or --save-every-iter)\n"
+               "                [--dangling-to-seeds]  (with --seed-set or --seed-queue: a set's dangling mass returns to\n"
+               "                its own seeds instead of all URLs; a set whose teleport terms sum to 0 or overflow keeps the\n"
+               "                uniform term; the whole run's mode, not a set's; --seeds keeps the uniform term)\n");
   std::exit(2);
 }
 
@@ -134,6 +146,7 @@ Options parse(int argc, char **argv) {
     else if (a == "--quiet") o.quiet = true;
     else if (a == "--stats") o.stats = true;
     else if (a == "--exclude-seeds") o.exclude_seeds = true;
+    else if (a == "--dangling-to-seeds") o.dangling_to_seeds = true;
     else if (a == "--dangling=local") o.flags = PR_DANGLING_LOCAL;
     else if (a == "--dangling=none") o.flags = PR_DANGLING_NONE;
     else if (a == "--device" && i + 1 < argc) o.device = std::atoi(argv[++i]);
@@ -177,6 +190,8 @@ Options parse(int argc, char **argv) {
   }
   if (o.path.empty()) usage("missing input path");
   if (o.iterations < 0) usage("iterations must be >= 0");
+  if (o.dangling_to_seeds && o.seed_sets.empty() && o.seed_queue.empty())
+    usage("--dangling-to-seeds needs --seed-set or --seed-queue");
   if (!o.seed_queue.empty()) {
     if (!o.seeds.empty() || !o.seed_sets.empty() || !o.devices.empty() || !o.resume.empty() || o.save_every)
       usage("--seed-queue does not combine with --seeds, --seed-set, --devices, --resume or --save-every-iter");
@@ -286,6 +301,7 @@ int run_seed_sets(const Options &o, const prh_edges *edges, const std::vector<Se
   pr_batch *b = nullptr;
   int rc = pr_graph_create(o.device, V, prh_n_edges(edges), prh_src(edges), prh_dst(edges), o.flags, &g);
   if (rc == PR_OK) rc = pr_batch_create(g, (int32_t)sets.size(), &b);
+  if (rc == PR_OK && o.dangling_to_seeds) rc = pr_batch_set_dangling(b, PR_BATCH_DANGLING_TELEPORT);
   for (size_t j = 0; j < sets.size() && rc == PR_OK; ++j)
     rc = pr_batch_set_teleport_sparse(b, (int32_t)j, sets[j].n, sets[j].ids, sets[j].values.data(), 0.0);
   if (rc == PR_OK) rc = pr_batch_reset(b, 0.15, 0.85, nullptr);
@@ -425,6 +441,7 @@ int run_seed_queue(const Options &o, const prh_edges *edges, const std::vector<s
   pr_graph *g = nullptr;
   int rc = pr_graph_create(o.device, V, prh_n_edges(edges), prh_src(edges), prh_dst(edges), o.flags, &g);
   if (rc == PR_OK) rc = pr_batch_create(g, width, &job.b);
+  if (rc == PR_OK && o.dangling_to_seeds) rc = pr_batch_set_dangling(job.b, PR_BATCH_DANGLING_TELEPORT);
   if (rc == PR_OK) rc = pr_batch_reset(job.b, 0.15, 0.85, nullptr);
   if (rc == PR_OK) rc = pr_batch_run_queue(job.b, (int32_t)Q, queries.data(), o.iterations, o.tol, nullptr, on_set_done, &job);
   if (rc == PR_OK) rc = job.rc;

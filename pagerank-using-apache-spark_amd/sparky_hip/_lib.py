@@ -65,10 +65,15 @@ EXPORTED = [
     "pr_batch_sync", "pr_batch_get_ranks", "pr_batch_get_norms", "pr_batch_get_topk", "pr_batch_info",
     "pr_batch_destroy", "pr_batch_set_exclude", "pr_batch_get_topk_all", "pr_batch_step_until",
     "pr_batch_reset_column", "pr_batch_step_until_any", "pr_batch_run_queue",
+    "pr_batch_set_dangling", "pr_batch_get_dangling", "pr_batch_get_teleport_sums",
 ]
 # pr_batch_info, in order
 BATCH_INFO_NAMES = ["width", "stride", "n_units", "n_long_rows", "device_bytes", "iters", "last_step_ns"]
 BATCH_MAX_WIDTH = 16
+# pr_batch_set_dangling's modes (PR_BATCH_DANGLING_*), by the name PageRankBatch.set_dangling takes
+PR_BATCH_DANGLING_UNIFORM = 0
+PR_BATCH_DANGLING_TELEPORT = 1
+BATCH_DANGLING_MODES = {"uniform": PR_BATCH_DANGLING_UNIFORM, "teleport": PR_BATCH_DANGLING_TELEPORT}
 
 ITER_CB = ctypes.CFUNCTYPE(None, ctypes.c_int32, ctypes.POINTER(ctypes.c_double), ctypes.c_double,
                            ctypes.c_double, ctypes.c_double, ctypes.c_void_p)
@@ -180,6 +185,11 @@ def load() -> ctypes.CDLL:
         "pr_batch_run_queue": ([P, i32, P, i32, dbl, P, P, P], ctypes.c_int),
         # internal: pr_batch_step_until_any with the block size and the enqueued / executed counts
         "pr_batch_step_until_any_ex": ([P, u32, i32, dbl, i32, P, P, P], ctypes.c_int),
+        "pr_batch_set_dangling": ([P, i32], ctypes.c_int),
+        "pr_batch_get_dangling": ([P, P], ctypes.c_int),
+        "pr_batch_get_teleport_sums": ([P, P], ctypes.c_int),
+        # internal: pr_batch_get_ranks for any column of the layout, [0, stride) -- the padding columns too
+        "pr_batch_get_ranks_ex": ([P, i32, P], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         if name in OPTIONAL and not hasattr(L, name):

@@ -10,6 +10,8 @@ all columns; ``set_exclude(column, ids)`` leaves vertices (a seed set, known ite
 column's lists.  ``step_until(max_iterations, tol)`` stops every column at its own convergence, decided
 on the device.  ``run_queue(queries, max_iterations, tol)`` serves any number of seed sets through the
 columns, refilling a column (``reset_column``) as soon as its query is done (``step_until_any``).
+``set_dangling("teleport")`` returns every column's dangling mass along its own teleport vector
+instead of spreading it over all vertices; ``teleport_sums()`` reports the vectors' sums it divides by.
 """
 from __future__ import annotations
 
@@ -62,6 +64,30 @@ class PageRankBatch:
         i, v = _sparse_arrays(ids, values)
         check(_lib.load().pr_batch_set_teleport_sparse(self._h, int(column), int(i.shape[0]), _ptr(i), _ptr(v),
                                                        float(rest)))
+
+    def set_dangling(self, mode: str) -> None:
+        """pr_batch_set_dangling: "uniform" (the default: every vertex receives dc_j / N) or "teleport"
+        (column j's dangling mass returns along its teleport vector: the term is dc_j / ts_j * t_j[v]
+        with ts_j = sum(t_j); a column without a vector, or whose vector sums to 0 or overflows, keeps
+        the uniform term).  The batch's mode: it holds for step, step_until, step_until_any and
+        run_queue from the next iteration on, and survives reset().  Waits for the enqueued steps."""
+        if mode not in _lib.BATCH_DANGLING_MODES:
+            raise ValueError('mode must be "uniform" or "teleport"')
+        check(_lib.load().pr_batch_set_dangling(self._h, _lib.BATCH_DANGLING_MODES[mode]))
+
+    @property
+    def dangling(self) -> str:
+        """The mode set_dangling() set: "uniform" or "teleport"."""
+        m = ctypes.c_int32(0)
+        check(_lib.load().pr_batch_get_dangling(self._h, ctypes.byref(m)))
+        return next(k for k, v in _lib.BATCH_DANGLING_MODES.items() if v == m.value)
+
+    def teleport_sums(self) -> np.ndarray:
+        """pr_batch_get_teleport_sums: float64[width], the sum ts_j of every column's teleport vector
+        as the device forms it (a fixed order; 0.0 for a column without a vector)."""
+        out = np.zeros(self.width, np.float64)
+        check(_lib.load().pr_batch_get_teleport_sums(self._h, _ptr(out)))
+        return out
 
     # -- iteration ---------------------------------------------------------------------------
     def reset(self, *, teleport: float = 0.15, damping: float = 0.85, init_ranks=None) -> None:
@@ -164,6 +190,13 @@ class PageRankBatch:
     def ranks(self, column: int) -> np.ndarray:
         out = np.zeros(max(self.n_vertices, 1), np.float64)
         check(_lib.load().pr_batch_get_ranks(self._h, int(column), _ptr(out)))
+        return out[: self.n_vertices]
+
+    def _ranks_ex(self, column: int) -> np.ndarray:
+        """The library's internal entry point behind ranks() for any column of the layout, [0, stride):
+        a padding column (>= width) holds zeros.  For tests."""
+        out = np.zeros(max(self.n_vertices, 1), np.float64)
+        check(_lib.load().pr_batch_get_ranks_ex(self._h, int(column), _ptr(out)))
         return out[: self.n_vertices]
 
     def norms(self):

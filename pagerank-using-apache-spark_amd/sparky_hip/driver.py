@@ -3,7 +3,7 @@
 CLI: ``python -m sparky_hip <input-path> [iterations=10] [--format edges|ccjson]
 [--out DIR] [--save-every-iter] [--dangling=local|none] [--device N] [--quiet]
 [--resume DIR/PageRank<i>] [--devices D0,D1,...] [--top K] [--seeds FILE] [--seed-set FILE]...
-[--exclude-seeds] [--tol X] [--seed-queue LISTFILE [--slots W]]``
+[--exclude-seeds] [--tol X] [--seed-queue LISTFILE [--slots W]] [--dangling-to-seeds]``
 
 * input: text edge list, ``src dst`` per line; a single-token line ``src`` is a record without
   ``a`` links (Sparky.java:114-118).  Tokens (URLs) are taken verbatim and interned to dense
@@ -55,6 +55,13 @@ CLI: ``python -m sparky_hip <input-path> [iterations=10] [--form
   ``--top`` listing (with ``--exclude-seeds`` without its own seeds) -- the lines ``--seed-set FILE
   --tol X --top K`` prints for that file alone.  ``--out DIR`` writes set q to
   ``DIR/seedset<q>/PageRank<n - 1>``.  Same bytes as the C++ CLI.
+* ``--dangling-to-seeds`` (needs ``--seed-set`` or ``--seed-queue``, else a usage error before any GPU
+  work): every set's dangling mass returns to that set's own seeds, in proportion to their weights
+  (``PageRankBatch.set_dangling("teleport")``), instead of being spread over all URLs: a URL the
+  seeds cannot reach keeps rank 0.  A set whose teleport terms sum to 0 or overflow keeps the uniform term; with
+  ``--dangling=none`` there is no dangling mass and the option changes nothing.  The mode is the
+  whole run's, not a set's; ``--seeds`` (the engine's own iteration) keeps the uniform term.  Output
+  format unchanged, same bytes as the C++ CLI.
 """
 from __future__ import annotations
 
@@ -203,6 +210,8 @@ def _run_seed_sets(edges, a, sets, top, out) -> None:
 
     with PageRankGraph(edges.n_vertices, edges.src, edges.dst, device=a.device, dangling=a.dangling) as g:
         with PageRankBatch(g, len(sets)) as b:
+            if a.dangling_to_seeds:
+                b.set_dangling("teleport")
             for j, (ids, values) in enumerate(sets):
                 b.set_teleport_sparse(j, ids, values)
             b.reset()
@@ -257,6 +266,8 @@ def _run_seed_queue(edges, a, files, sets, top, out) -> None:
     queries = [(ids, values, 0.0, ids if a.exclude_seeds else None) for ids, values in sets]
     with PageRankGraph(edges.n_vertices, edges.src, edges.dst, device=a.device, dangling=a.dangling) as g:
         with PageRankBatch(g, width) as b:
+            if a.dangling_to_seeds:
+                b.set_dangling("teleport")
             b.reset()
 
             def on_done(q, column, rec):
@@ -304,6 +315,10 @@ def main(argv=None) -> int:
                     help="a queue of seed sets (one seed-file path per line) served by --slots batch columns that are "
                          "refilled as sets converge; needs --tol and --top")
     ap.add_argument("--slots", default=None, metavar="W", help="with --seed-queue: the batch width, 1..16")
+    ap.add_argument("--dangling-to-seeds", action="store_true",
+                    help="with --seed-set or --seed-queue: a set's dangling mass returns to its own seeds instead of "
+                         "all URLs; a set whose teleport terms sum to 0 or overflow keeps the uniform term; the whole run's "
+                         "mode, not a set's; --seeds keeps the uniform term")
     a = ap.parse_args(argv)
     if a.slots is not None:
         if not (a.slots.isdigit() and len(a.slots) <= 2 and 1 <= int(a.slots) <= 16):
@@ -318,6 +333,8 @@ def main(argv=None) -> int:
             ap.error("--tol: not a finite number >= 0")
         if not a.seed_set and a.seed_queue is None:
             ap.error("--tol needs --seed-set")
+    if a.dangling_to_seeds and not (a.seed_set or a.seed_queue is not None):
+        ap.error("--dangling-to-seeds needs --seed-set or --seed-queue")
     if a.seed_queue is not None:
         if a.seeds is not None or a.seed_set or a.devices is not None or a.resume or a.save_every_iter:
             ap.error("--seed-queue does not combine with --seeds, --seed-set, --devices, --resume or --save-every-iter")

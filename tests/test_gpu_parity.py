@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import sparky_rdd
+from gen_model import first_appearance as host_first_appearance
 
 pytestmark = pytest.mark.gpu
 
@@ -220,19 +221,6 @@ def test_edge_cases(hip, oracle_c):
     assert e.value.code == -1
     with pytest.raises(hip.PageRankError):
         hip.PageRankGraph(3, np.array([0], np.int32), np.array([1], np.int32))  # ID 2 never appears
-
-
-def host_first_appearance(src, dst):
-    occ = np.stack([src, dst], 1).ravel()
-    pos = np.arange(occ.size)
-    keep = occ >= 0
-    labels, first = np.unique(occ[keep], return_index=True)
-    order = np.argsort(pos[keep][first], kind="stable")
-    newid = np.full(labels.max() + 1 if labels.size else 1, -1, np.int64)
-    newid[labels[order]] = np.arange(labels.size)
-    s2 = newid[src]
-    d2 = np.where(dst >= 0, newid[np.maximum(dst, 0)], -1)
-    return labels.size, s2.astype(np.int32), d2.astype(np.int32)
 
 
 @pytest.mark.parametrize("gen,scale,ef,layout", [("rmat", 14, 16, "auto"), ("er", 13, 16, "auto"),

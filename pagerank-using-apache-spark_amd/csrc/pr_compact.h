@@ -11,6 +11,7 @@
 
 namespace pr {
 
+// tests/build_model.py compact_shape restates the tile and compact_index's 2048-workgroup cap.
 constexpr int kCompactThreads = 256;
 constexpr int kCompactIPT = 8;
 constexpr int kCompactTile = kCompactThreads * kCompactIPT;

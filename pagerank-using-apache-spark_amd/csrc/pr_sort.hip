@@ -19,6 +19,7 @@
 namespace pr {
 namespace {
 
+// tests/build_model.py sort_shape restates the tile, the workgroup cap and the 8-bit digit.
 constexpr int kSortThreads = 256;
 constexpr int kSortKPT = 8;
 constexpr int kTile = kSortThreads * kSortKPT;  // 2048 keys

@@ -21,15 +21,20 @@
 // a column's dangling mass -- has an order that depends on the graph and the stride only.  No
 // floating-point atomics anywhere.
 //
-// pr_batch_step_until runs the same iteration through sibling kernels (k_batch_units_until,
-// k_batch_long_until, k_batch_finalize_until) that read an active mask (pr_batch_until.h) from
-// device memory.  A column whose bit is clear is frozen: its lanes still take part in every row sum, shuffle and barrier, but
-// store no rank, no L1 and no new dangling sum; instead they copy their contributions cin -> cout and
-// the finalize step copies dc_in -> dc_out, so that both double buffers stay valid whatever the
-// parity of the iteration the column stopped at.  A fourth, one-thread launch (k_batch_decide) runs
-// after the finalize step, counts the iteration for the active columns and clears the bits of those
-// whose L1 is within tol; no kernel of an iteration can therefore see that iteration's own decision.
-// With an empty mask every kernel returns at entry.  pr_batch_step launches none of these.
+// The unit and the long-row kernel are each written once, as a body (units_body, long_body) with two
+// template switches, UNTIL and TD; the __global__ templates named here are the body's forms and hold
+// no code of their own, and launch_iteration picks the form.
+//
+// pr_batch_step_until runs the iteration in its UNTIL form (k_batch_units_until, k_batch_long_until)
+// and through k_batch_finalize_until, which read an active mask (pr_batch_until.h) from device
+// memory.  A column whose bit is clear is frozen: its lanes still take part in every row sum, shuffle
+// and barrier, but store no rank, no L1 and no new dangling sum; instead they copy their
+// contributions cin -> cout and the finalize step copies dc_in -> dc_out, so that both double
+// buffers stay valid whatever the parity of the iteration the column stopped at.  A fourth,
+// one-thread launch (k_batch_decide) runs after the finalize step, counts the iteration for the
+// active columns and clears the bits of those whose L1 is within tol; no kernel of an iteration can
+// therefore see that iteration's own decision.  With an empty mask every kernel returns at entry.
+// pr_batch_step launches none of these.
 //
 // pr_batch_run_queue (scheduler: pr_batch_queue.h) refills columns one at a time: k_batch_set_col and
 // k_batch_scatter_col write a sparse teleport vector into T on the device, k_batch_reset_col and
@@ -39,10 +44,11 @@
 // which a column converged.
 //
 // pr_batch_set_dangling(PR_BATCH_DANGLING_TELEPORT) replaces the unit and long-row kernels of all of
-// the above by k_batch_units_td / k_batch_long_td, which return column j's dangling mass along its
-// teleport vector (q_j * t[p], q_j = dc_j / ts_j) where ts_j -- the vector's sum, formed by
-// k_batch_tsum_col in k_batch_reset_col's order whenever a vector changed -- is finite and not 0, and
-// add the uniform dc_j / N otherwise (pr_batch_dangling.h).  In the default mode none of these runs.
+// the above by their TD forms, k_batch_units_td / k_batch_long_td, which return column j's dangling
+// mass along its teleport vector (q_j * t[p], q_j = dc_j / ts_j) where ts_j -- the vector's sum,
+// formed by k_batch_tsum_col in k_batch_reset_col's order whenever a vector changed -- is finite and
+// not 0, and add the uniform dc_j / N otherwise (pr_batch_dangling.h).  In the default mode none of
+// these runs.
 //
 // The batch only reads the graph's canon_* buffers; it launches none of the graph's kernels and
 // owns its stream and all its state.
@@ -171,32 +177,61 @@ __device__ __forceinline__ double row_sum(const int32_t *__restrict__ col, const
   return group_sum<S>(acc);
 }
 
+// What a lane adds to its in-link sums for column j's dangling mass, formed once at entry from
+// dc = dc_j and, in the teleport form, ts = ts_j (ts[0..S) holds the sums of the columns' teleport
+// vectors: k_batch_tsum_col; 0 for a column without one and for padding).  Uniform form
+// (TD == false): q = dc_j / N, added as it is.  Teleport form: the lane picks, as a select, its
+// factor q = dc_j / ts_j (use: an element adds q * t[p]) or the uniform term (pr_batch_dangling.h).
+// Nothing that shuffles or waits depends on the pick.
+struct LaneTerm {
+  bool use;
+  double q;
+};
+template <bool TD>
+__device__ __forceinline__ LaneTerm lane_term(double dc, double n_vertices, double ts) {
+  const bool use = TD && batch_dangling_uses_teleport(ts);
+  return {use, TD ? batch_dangling_factor(use, dc, ts, n_vertices) : dc / n_vertices};
+}
+
 // Element (v, j) of a row whose in-link sum is Sv: the update, the new contribution and the
-// column's dangling / L1 partials.
+// column's dangling / L1 partials.  Under an active mask (UNTIL) an element of a frozen column
+// (act == false) only carries its contribution over to the buffer the next iteration reads (d == 0
+// elements are 0 in both buffers).
+template <bool UNTIL, bool TD>
 __device__ __forceinline__ void update_elem(const BatchArgs &a, int64_t v, int64_t p, double Sv, double rold,
-                                            uint32_t f, double tdc, double &dcp, double &l1p) {
-  const double rn = batch_affine(Sv, tdc, a.t[p], a.damping);
-  a.r[p] = rn;
-  const int32_t d = a.deg[v];
-  if (d > 0) a.cout[p] = __ddiv_rn(rn, (double)d);
-  else if ((f & PR_VF_SINK) && !a.dangling_none) dcp = __dadd_rn(dcp, rn);
-  l1p = __dadd_rn(l1p, fabs(rn - rold));
+                                            uint32_t f, LaneTerm lt, bool act, double &dcp, double &l1p) {
+  if (!UNTIL || act) {
+    const double tp = a.t[p];
+    const double rn = batch_affine(Sv, TD && lt.use ? batch_dangling_term(lt.q, tp) : lt.q, tp, a.damping);
+    a.r[p] = rn;
+    const int32_t d = a.deg[v];
+    if (d > 0) a.cout[p] = __ddiv_rn(rn, (double)d);
+    else if ((f & PR_VF_SINK) && !a.dangling_none) dcp = __dadd_rn(dcp, rn);
+    l1p = __dadd_rn(l1p, fabs(rn - rold));
+  } else if (a.deg[v] > 0) {
+    a.cout[p] = a.cin[p];
+  }
 }
 
-// update_elem under an active mask: an element of a frozen column (act == false) only carries its
-// contribution over to the buffer the next iteration reads (d == 0 elements are 0 in both buffers).
-__device__ __forceinline__ void update_elem_until(const BatchArgs &a, int64_t v, int64_t p, double Sv, double rold,
-                                                  uint32_t f, double tdc, bool act, double &dcp, double &l1p) {
-  if (act) update_elem(a, v, p, Sv, rold, f, tdc, dcp, l1p);
-  else if (a.deg[v] > 0) a.cout[p] = a.cin[p];
-}
-
-template <int S>
-__global__ __launch_bounds__(kWave) void k_batch_units(BatchArgs a) {
+// The body of the unit kernels below.  UNTIL: the iteration runs under the active mask of `us`
+// (pr_batch_until.h), one word that is the same for every lane, so an empty mask is a uniform exit --
+// the only early one; everything that shuffles or waits at a barrier runs for frozen columns too.
+// TD: the teleport form of the dangling term (lane_term).  `a` comes by value, as a kernel holds it:
+// by reference the compiler splits the kernel-argument loads of the prologue and waits for them
+// twice (profiles/batch_refactor/).
+template <int S, bool UNTIL, bool TD>
+__device__ __forceinline__ void units_body(BatchArgs a, const double *__restrict__ ts,
+                                           const BatchUntilState *__restrict__ us) {
   constexpr int G = kWave / S;
   __shared__ double sS[kBatchUnitRows * S];
+  uint32_t m = 0xffffffffu;
+  if (UNTIL) {
+    m = us->mask;
+    if (m == 0) return;
+  }
   const int lane = threadIdx.x, g = lane / S, j = lane % S;
-  const double tdc = a.dc[j] / a.n_vertices;
+  const bool act = (m >> j) & 1u;
+  const LaneTerm lt = lane_term<TD>(a.dc[j], a.n_vertices, TD ? ts[j] : 0.0);
   double dcp = 0.0, l1p = 0.0;
   for (int64_t u = blockIdx.x; u < a.n_units; u += gridDim.x) {
     const BatchUnit un = a.units[u];
@@ -244,13 +279,13 @@ __global__ __launch_bounds__(kWave) void k_batch_units(BatchArgs a) {
       const int64_t v = (int64_t)un.row0 + idx / S, p = v * S + j;
       const uint32_t f = a.vflags[v];
       const double rold = a.r[p];
-      update_elem(a, v, p, (f & PR_VF_INDEG0) ? rold : sS[idx], rold, f, tdc, dcp, l1p);
+      update_elem<UNTIL, TD>(a, v, p, (f & PR_VF_INDEG0) ? rold : sS[idx], rold, f, lt, act, dcp, l1p);
     }
     __syncthreads();
   }
   dcp = group_sum<S>(dcp);
   l1p = group_sum<S>(l1p);
-  if (lane < S) {
+  if (lane < S) {  // a frozen column's partials are zeros that k_batch_finalize_until never reads
     a.part[((int64_t)blockIdx.x * 2) * S + j] = dcp;
     a.part[((int64_t)blockIdx.x * 2 + 1) * S + j] = l1p;
   }
@@ -276,11 +311,18 @@ __device__ __forceinline__ void block_col_part(double dcp, double l1p, double *_
   }
 }
 
-// One thread per (long row, column): the row's chunk partials in chunk order, then the update.
-template <int S>
-__global__ __launch_bounds__(kBatchThreads) void k_batch_long(BatchArgs a, const int32_t *__restrict__ long_row,
-                                                              const int32_t *__restrict__ long_p0, int64_t n_long,
-                                                              int64_t part_block0) {
+// The body of the long-row kernels below.  One thread per (long row, column): the row's chunk
+// partials in chunk order, then the update.  UNTIL and TD as in units_body; the empty mask's exit is
+// uniform and comes before the barrier of block_col_part.
+template <int S, bool UNTIL, bool TD>
+__device__ __forceinline__ void long_body(const BatchArgs &a, const int32_t *__restrict__ long_row,
+                                          const int32_t *__restrict__ long_p0, int64_t n_long, int64_t part_block0,
+                                          const double *__restrict__ ts, const BatchUntilState *__restrict__ us) {
+  uint32_t m = 0xffffffffu;
+  if (UNTIL) {
+    m = us->mask;
+    if (m == 0) return;
+  }
   const int64_t idx = (int64_t)blockIdx.x * kBatchThreads + threadIdx.x;
   const int64_t q = idx / S;
   const int j = threadIdx.x % S;
@@ -290,9 +332,49 @@ __global__ __launch_bounds__(kBatchThreads) void k_batch_long(BatchArgs a, const
     double acc = 0.0;
     for (int32_t k = p0; k < p1; ++k) acc = __dadd_rn(acc, a.chunk_part[(int64_t)k * S + j]);
     const int64_t v = long_row[q], p = v * S + j;
-    update_elem(a, v, p, acc, a.r[p], a.vflags[v], a.dc[j] / a.n_vertices, dcp, l1p);
+    const double rold = a.r[p];
+    const uint32_t f = a.vflags[v];
+    const LaneTerm lt = lane_term<TD>(a.dc[j], a.n_vertices, TD ? ts[j] : 0.0);
+    update_elem<UNTIL, TD>(a, v, p, acc, rold, f, lt, (m >> j) & 1u, dcp, l1p);
   }
   block_col_part<S>(dcp, l1p, a.part, part_block0 + blockIdx.x);
+}
+
+// The kernels of an iteration, one pair per form: plain (pr_batch_step), _until (under the active
+// mask), _td (PR_BATCH_DANGLING_TELEPORT; UNTIL selects the masked form, so the two templates stand
+// for four kernels).  Each is its body with the form's template arguments and nothing else.
+template <int S>
+__global__ __launch_bounds__(kWave) void k_batch_units(BatchArgs a) {
+  units_body<S, false, false>(a, nullptr, nullptr);
+}
+template <int S>
+__global__ __launch_bounds__(kWave) void k_batch_units_until(BatchArgs a, const BatchUntilState *__restrict__ us) {
+  units_body<S, true, false>(a, nullptr, us);
+}
+template <int S, bool UNTIL>
+__global__ __launch_bounds__(kWave) void k_batch_units_td(BatchArgs a, const double *__restrict__ ts,
+                                                          const BatchUntilState *__restrict__ us) {
+  units_body<S, UNTIL, true>(a, ts, us);
+}
+template <int S>
+__global__ __launch_bounds__(kBatchThreads) void k_batch_long(BatchArgs a, const int32_t *__restrict__ long_row,
+                                                              const int32_t *__restrict__ long_p0, int64_t n_long,
+                                                              int64_t part_block0) {
+  long_body<S, false, false>(a, long_row, long_p0, n_long, part_block0, nullptr, nullptr);
+}
+template <int S>
+__global__ __launch_bounds__(kBatchThreads) void k_batch_long_until(BatchArgs a, const int32_t *__restrict__ long_row,
+                                                                    const int32_t *__restrict__ long_p0, int64_t n_long,
+                                                                    int64_t part_block0,
+                                                                    const BatchUntilState *__restrict__ us) {
+  long_body<S, true, false>(a, long_row, long_p0, n_long, part_block0, nullptr, us);
+}
+template <int S, bool UNTIL>
+__global__ __launch_bounds__(kBatchThreads) void k_batch_long_td(BatchArgs a, const int32_t *__restrict__ long_row,
+                                                                 const int32_t *__restrict__ long_p0, int64_t n_long,
+                                                                 int64_t part_block0, const double *__restrict__ ts,
+                                                                 const BatchUntilState *__restrict__ us) {
+  long_body<S, UNTIL, true>(a, long_row, long_p0, n_long, part_block0, ts, us);
 }
 
 // Workgroup kind * S + j: column j's dangling (kind 0) or L1 (kind 1) partials of n_blocks
@@ -306,96 +388,6 @@ __global__ __launch_bounds__(kBatchThreads) void k_batch_finalize(const double *
   for (int64_t b = threadIdx.x; b < n_blocks; b += kBatchThreads) acc = __dadd_rn(acc, part[(b * 2 + kind) * S + j]);
   acc = block_sum<kBatchThreads>(acc, red);
   if (threadIdx.x == 0) (kind ? l1_out : dc_out)[j] = acc;
-}
-
-// ---- pr_batch_step_until's siblings of the three kernels above --------------------------------
-// The same statements in the same order (kept apart so that the kernels pr_batch_step launches
-// compile exactly as before), plus: the mask word read at entry, and update_elem_until in place of
-// update_elem.  Everything that shuffles or waits at a barrier runs for frozen columns too.
-template <int S>
-__global__ __launch_bounds__(kWave) void k_batch_units_until(BatchArgs a, const BatchUntilState *__restrict__ us) {
-  constexpr int G = kWave / S;
-  __shared__ double sS[kBatchUnitRows * S];
-  const uint32_t m = us->mask;  // one word, the same for every lane: a uniform exit
-  if (m == 0) return;
-  const int lane = threadIdx.x, g = lane / S, j = lane % S;
-  const bool act = (m >> j) & 1u;
-  const double tdc = a.dc[j] / a.n_vertices;
-  double dcp = 0.0, l1p = 0.0;
-  for (int64_t u = blockIdx.x; u < a.n_units; u += gridDim.x) {
-    const BatchUnit un = a.units[u];
-    if (un.rows < 0) {  // CHUNK
-      const double acc = row_sum<S>(a.col, a.cin, un.e0, un.e0 + un.n, g, j);
-      if (lane < S) a.chunk_part[(int64_t)un.slot * S + j] = acc;
-      continue;
-    }
-    const int rows = un.rows;
-    const long long rp_l = (long long)a.rowptr[(int64_t)un.row0 + (lane < rows ? lane : rows)];
-    const int64_t uend = un.e0 + un.n;
-    for (int k0 = 0; k0 < rows; k0 += G) {  // short rows
-      const int k = k0 + g;
-      const int ks = k < rows ? k : 0;
-      const int64_t b = __shfl(rp_l, ks, kWave);
-      const int64_t e1 = __shfl(rp_l, ks + 1 < kWave ? ks + 1 : kWave - 1, kWave);
-      const int64_t deg = k < rows ? (ks + 1 < rows ? e1 : uend) - b : 0;
-      if (deg > 0 && deg <= kBatchShortRow) {
-        int32_t c[kBatchShortRow];
-        double x[kBatchShortRow];
-#pragma unroll
-        for (int q = 0; q < kBatchShortRow; ++q) c[q] = q < deg ? a.col[b + q] : 0;
-#pragma unroll
-        for (int q = 0; q < kBatchShortRow; ++q) x[q] = q < deg ? a.cin[(int64_t)c[q] * S + j] : 0.0;
-        double acc = 0.0;
-#pragma unroll
-        for (int q = 0; q < kBatchShortRow; ++q)
-          if (q < deg) acc = __dadd_rn(acc, x[q]);
-        sS[k * S + j] = acc;
-      }
-    }
-    for (int k = 0; k < rows; ++k) {  // longer rows
-      const int64_t b = __shfl(rp_l, k, kWave);
-      const int64_t e = k + 1 < rows ? (int64_t)__shfl(rp_l, k + 1, kWave) : uend;
-      if (e - b <= kBatchShortRow) continue;
-      const double acc = row_sum<S>(a.col, a.cin, b, e, g, j);
-      if (lane < S) sS[k * S + j] = acc;
-    }
-    __syncthreads();
-    const int total = rows * S;
-    for (int idx = lane; idx < total; idx += kWave) {
-      const int64_t v = (int64_t)un.row0 + idx / S, p = v * S + j;
-      const uint32_t f = a.vflags[v];
-      const double rold = a.r[p];
-      update_elem_until(a, v, p, (f & PR_VF_INDEG0) ? rold : sS[idx], rold, f, tdc, act, dcp, l1p);
-    }
-    __syncthreads();
-  }
-  dcp = group_sum<S>(dcp);
-  l1p = group_sum<S>(l1p);
-  if (lane < S) {  // a frozen column's partials are zeros that k_batch_finalize_until never reads
-    a.part[((int64_t)blockIdx.x * 2) * S + j] = dcp;
-    a.part[((int64_t)blockIdx.x * 2 + 1) * S + j] = l1p;
-  }
-}
-
-template <int S>
-__global__ __launch_bounds__(kBatchThreads) void k_batch_long_until(BatchArgs a, const int32_t *__restrict__ long_row,
-                                                                    const int32_t *__restrict__ long_p0, int64_t n_long,
-                                                                    int64_t part_block0,
-                                                                    const BatchUntilState *__restrict__ us) {
-  const uint32_t m = us->mask;
-  if (m == 0) return;  // uniform, and before the barrier of block_col_part
-  const int64_t idx = (int64_t)blockIdx.x * kBatchThreads + threadIdx.x;
-  const int64_t q = idx / S;
-  const int j = threadIdx.x % S;
-  double dcp = 0.0, l1p = 0.0;
-  if (q < n_long) {
-    const int32_t p0 = long_p0[q], p1 = long_p0[q + 1];
-    double acc = 0.0;
-    for (int32_t k = p0; k < p1; ++k) acc = __dadd_rn(acc, a.chunk_part[(int64_t)k * S + j]);
-    const int64_t v = long_row[q], p = v * S + j;
-    update_elem_until(a, v, p, acc, a.r[p], a.vflags[v], a.dc[j] / a.n_vertices, (m >> j) & 1u, dcp, l1p);
-  }
-  block_col_part<S>(dcp, l1p, a.part, part_block0 + blockIdx.x);
 }
 
 // k_batch_finalize under an active mask.  An active column also records the dc this iteration used
@@ -456,158 +448,49 @@ __global__ __launch_bounds__(kWave) void k_batch_decide_any(BatchUntilState *__r
   us->mask = batch_any_decide(m, l1, tol, width, qs);
 }
 
-// ---- PR_BATCH_DANGLING_TELEPORT's siblings of the unit and long-row kernels --------------------
-// Again the same statements in the same order, kept apart so that the kernels above compile exactly
-// as before.  UNTIL selects the masked form (k_batch_units_until / k_batch_long_until's extras), so
-// the two templates stand for four kernels; the finalize and decide kernels are shared with uniform
-// mode, which they do not see.  ts[0..S) holds the sums of the columns' teleport vectors
-// (k_batch_tsum_col; 0 for a column without one and for padding).  A lane picks, once at entry and
-// as a select, its factor q_j = dc_j / ts_j or the uniform term dc_j / N (pr_batch_dangling.h);
-// an element then adds q_j * t[p] or that term.  Nothing that shuffles or waits depends on the pick.
-__device__ __forceinline__ void update_elem_td(const BatchArgs &a, int64_t v, int64_t p, double Sv, double rold,
-                                               uint32_t f, bool use, double qf, bool act, double &dcp, double &l1p) {
-  if (act) {
-    const double tp = a.t[p];
-    const double rn = batch_affine(Sv, use ? batch_dangling_term(qf, tp) : qf, tp, a.damping);
-    a.r[p] = rn;
-    const int32_t d = a.deg[v];
-    if (d > 0) a.cout[p] = __ddiv_rn(rn, (double)d);
-    else if ((f & PR_VF_SINK) && !a.dangling_none) dcp = __dadd_rn(dcp, rn);
-    l1p = __dadd_rn(l1p, fabs(rn - rold));
-  } else if (a.deg[v] > 0) {
-    a.cout[p] = a.cin[p];
+// The first half of a one-column sum (k_batch_tsum_col, k_batch_reset_col): the values x of the
+// workgroup's threads of column j (threadIdx.x % S == j), added in thread order -- block_col_part's
+// order for that column -- into part1[blockIdx.x].  part1 is a dense array of its own shape in the
+// part scratch: every launch that uses the scratch is on the batch's stream, so they take turns.
+template <int S>
+__device__ __forceinline__ void block_one_col_part(double x, int j, double *__restrict__ part1) {
+  __shared__ double sh[kBatchThreads];
+  sh[threadIdx.x] = x;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = 0.0;
+    for (int k = j; k < kBatchThreads; k += S) s = __dadd_rn(s, sh[k]);
+    part1[blockIdx.x] = s;
   }
 }
 
-template <int S, bool UNTIL>
-__global__ __launch_bounds__(kWave) void k_batch_units_td(BatchArgs a, const double *__restrict__ ts,
-                                                          const BatchUntilState *__restrict__ us) {
-  constexpr int G = kWave / S;
-  __shared__ double sS[kBatchUnitRows * S];
-  uint32_t m = 0xffffffffu;
-  if (UNTIL) {
-    m = us->mask;  // one word, the same for every lane: a uniform exit
-    if (m == 0) return;
-  }
-  const int lane = threadIdx.x, g = lane / S, j = lane % S;
-  const bool act = (m >> j) & 1u;
-  const double tsj = ts[j];
-  const bool use = batch_dangling_uses_teleport(tsj);
-  const double qf = batch_dangling_factor(use, a.dc[j], tsj, a.n_vertices);
-  double dcp = 0.0, l1p = 0.0;
-  for (int64_t u = blockIdx.x; u < a.n_units; u += gridDim.x) {
-    const BatchUnit un = a.units[u];
-    if (un.rows < 0) {  // CHUNK
-      const double acc = row_sum<S>(a.col, a.cin, un.e0, un.e0 + un.n, g, j);
-      if (lane < S) a.chunk_part[(int64_t)un.slot * S + j] = acc;
-      continue;
-    }
-    const int rows = un.rows;
-    const long long rp_l = (long long)a.rowptr[(int64_t)un.row0 + (lane < rows ? lane : rows)];
-    const int64_t uend = un.e0 + un.n;
-    for (int k0 = 0; k0 < rows; k0 += G) {  // short rows
-      const int k = k0 + g;
-      const int ks = k < rows ? k : 0;
-      const int64_t b = __shfl(rp_l, ks, kWave);
-      const int64_t e1 = __shfl(rp_l, ks + 1 < kWave ? ks + 1 : kWave - 1, kWave);
-      const int64_t deg = k < rows ? (ks + 1 < rows ? e1 : uend) - b : 0;
-      if (deg > 0 && deg <= kBatchShortRow) {
-        int32_t c[kBatchShortRow];
-        double x[kBatchShortRow];
-#pragma unroll
-        for (int q = 0; q < kBatchShortRow; ++q) c[q] = q < deg ? a.col[b + q] : 0;
-#pragma unroll
-        for (int q = 0; q < kBatchShortRow; ++q) x[q] = q < deg ? a.cin[(int64_t)c[q] * S + j] : 0.0;
-        double acc = 0.0;
-#pragma unroll
-        for (int q = 0; q < kBatchShortRow; ++q)
-          if (q < deg) acc = __dadd_rn(acc, x[q]);
-        sS[k * S + j] = acc;
-      }
-    }
-    for (int k = 0; k < rows; ++k) {  // longer rows
-      const int64_t b = __shfl(rp_l, k, kWave);
-      const int64_t e = k + 1 < rows ? (int64_t)__shfl(rp_l, k + 1, kWave) : uend;
-      if (e - b <= kBatchShortRow) continue;
-      const double acc = row_sum<S>(a.col, a.cin, b, e, g, j);
-      if (lane < S) sS[k * S + j] = acc;
-    }
-    __syncthreads();
-    const int total = rows * S;
-    for (int idx = lane; idx < total; idx += kWave) {
-      const int64_t v = (int64_t)un.row0 + idx / S, p = v * S + j;
-      const uint32_t f = a.vflags[v];
-      const double rold = a.r[p];
-      update_elem_td(a, v, p, (f & PR_VF_INDEG0) ? rold : sS[idx], rold, f, use, qf, act, dcp, l1p);
-    }
-    __syncthreads();
-  }
-  dcp = group_sum<S>(dcp);
-  l1p = group_sum<S>(l1p);
-  if (lane < S) {
-    a.part[((int64_t)blockIdx.x * 2) * S + j] = dcp;
-    a.part[((int64_t)blockIdx.x * 2 + 1) * S + j] = l1p;
-  }
-}
-
-template <int S, bool UNTIL>
-__global__ __launch_bounds__(kBatchThreads) void k_batch_long_td(BatchArgs a, const int32_t *__restrict__ long_row,
-                                                                 const int32_t *__restrict__ long_p0, int64_t n_long,
-                                                                 int64_t part_block0, const double *__restrict__ ts,
-                                                                 const BatchUntilState *__restrict__ us) {
-  uint32_t m = 0xffffffffu;
-  if (UNTIL) {
-    m = us->mask;
-    if (m == 0) return;  // uniform, and before the barrier of block_col_part
-  }
-  const int64_t idx = (int64_t)blockIdx.x * kBatchThreads + threadIdx.x;
-  const int64_t q = idx / S;
-  const int j = threadIdx.x % S;
-  double dcp = 0.0, l1p = 0.0;
-  if (q < n_long) {
-    const int32_t p0 = long_p0[q], p1 = long_p0[q + 1];
-    double acc = 0.0;
-    for (int32_t k = p0; k < p1; ++k) acc = __dadd_rn(acc, a.chunk_part[(int64_t)k * S + j]);
-    const int64_t v = long_row[q], p = v * S + j;
-    const double tsj = ts[j];
-    const bool use = batch_dangling_uses_teleport(tsj);
-    update_elem_td(a, v, p, acc, a.r[p], a.vflags[v], use, batch_dangling_factor(use, a.dc[j], tsj, a.n_vertices),
-                   (m >> j) & 1u, dcp, l1p);
-  }
-  block_col_part<S>(dcp, l1p, a.part, part_block0 + blockIdx.x);
+// The second half, in one workgroup (k_batch_tsum_finalize, k_batch_finalize_col): k_batch_finalize's
+// strided sums over part1[0..n_blocks) and the same block_sum.
+__device__ __forceinline__ double one_col_total(const double *__restrict__ part1, int64_t n_blocks) {
+  __shared__ double red[kBatchThreads / kWave];
+  double acc = 0.0;
+  for (int64_t b = threadIdx.x; b < n_blocks; b += kBatchThreads) acc = __dadd_rn(acc, part1[b]);
+  return block_sum<kBatchThreads>(acc, red);
 }
 
 // The sum of column j of T for teleport mode, in k_batch_reset_col's traversal (launched with
 // k_batch_reset's grid): the threads with threadIdx.x % S == j add the elements they visit there, in
-// that order; the workgroup's sum of its threads' partials, in thread order, goes to
-// part1[blockIdx.x].  The order depends on V and S only, not on j: thread S * m + j of workgroup b
-// visits the vertices thread S * m of it would.  part1 is the part scratch: every launch that uses
-// it is on the batch's stream, so they take turns.
+// that order.  The order depends on V and S only, not on j: thread S * m + j of workgroup b visits
+// the vertices thread S * m of it would.
 template <int S>
 __global__ __launch_bounds__(kBatchThreads) void k_batch_tsum_col(int64_t V, int j, const double *__restrict__ t,
                                                                   double *__restrict__ part1) {
-  __shared__ double sh[kBatchThreads];
   const int tx = threadIdx.x;
   double acc = 0.0;
   if (tx % S == j)
     for (int64_t p = (int64_t)blockIdx.x * kBatchThreads + tx; p < V * S; p += (int64_t)gridDim.x * kBatchThreads)
       acc = __dadd_rn(acc, t[p]);
-  sh[tx] = acc;
-  __syncthreads();
-  if (tx == 0) {
-    double x = 0.0;
-    for (int k = j; k < kBatchThreads; k += S) x = __dadd_rn(x, sh[k]);
-    part1[blockIdx.x] = x;
-  }
+  block_one_col_part<S>(acc, j, part1);
 }
 
-// k_batch_finalize_col's strided sums and block_sum over part1, into ts[j].
 __global__ __launch_bounds__(kBatchThreads) void k_batch_tsum_finalize(const double *__restrict__ part1, int64_t n_blocks,
                                                                        int j, double *__restrict__ ts) {
-  __shared__ double red[kBatchThreads / kWave];
-  double acc = 0.0;
-  for (int64_t b = threadIdx.x; b < n_blocks; b += kBatchThreads) acc = __dadd_rn(acc, part1[b]);
-  acc = block_sum<kBatchThreads>(acc, red);
+  const double acc = one_col_total(part1, n_blocks);
   if (threadIdx.x == 0) ts[j] = acc;
 }
 
@@ -641,16 +524,14 @@ __global__ __launch_bounds__(kBatchThreads) void k_batch_reset(int64_t V, int wi
 // (threadIdx.x % S == j) visit the elements they visit there, in the same order, so a thread's
 // dangling partial has the same bits; the others only wait at the barrier.  T stays as it is.  Both
 // contribution buffers get the new contributions (the column may be frozen in the next iteration,
-// which copies cin -> cout only where out_deg > 0).  The workgroup's sum, in block_col_part's order,
-// goes to part1[blockIdx.x]: a dense array of its own shape in the part scratch, which no iteration
-// is using (the caller has waited for the stream).
+// which copies cin -> cout only where out_deg > 0).  The workgroup's sum goes to part1[blockIdx.x],
+// in the part scratch, which no iteration is using (the caller has waited for the stream).
 template <int S>
 __global__ __launch_bounds__(kBatchThreads) void k_batch_reset_col(int64_t V, int j, const double *__restrict__ init,
                                                                    const int32_t *__restrict__ deg,
                                                                    const uint8_t *__restrict__ vflags, int dangling_none,
                                                                    double *__restrict__ r, double *__restrict__ c0,
                                                                    double *__restrict__ c1, double *__restrict__ part1) {
-  __shared__ double sh[kBatchThreads];
   const int t = threadIdx.x;
   double dcp = 0.0;
   if (t % S == j)
@@ -664,27 +545,18 @@ __global__ __launch_bounds__(kBatchThreads) void k_batch_reset_col(int64_t V, in
       c1[p] = c;
       if (d == 0 && (vflags[v] & PR_VF_SINK) && !dangling_none) dcp = __dadd_rn(dcp, x);
     }
-  sh[t] = dcp;
-  __syncthreads();
-  if (t == 0) {
-    double x = 0.0;
-    for (int k = j; k < kBatchThreads; k += S) x = __dadd_rn(x, sh[k]);
-    part1[blockIdx.x] = x;
-  }
+  block_one_col_part<S>(dcp, j, part1);
 }
 
-// k_batch_finalize's dangling workgroup for one column over part1: the same strided sums and the
-// same block_sum.  The sum goes to both dc buffers (either may be read next, and a frozen column
-// copies one to the other) and to dcu, so that pr_batch_get_norms finds it whatever advanced the
-// batch last; the column's L1 is the 0 that k_batch_finalize sums after a reset.
+// k_batch_finalize's dangling workgroup for one column over part1.  The sum goes to both dc buffers
+// (either may be read next, and a frozen column copies one to the other) and to dcu, so that
+// pr_batch_get_norms finds it whatever advanced the batch last; the column's L1 is the 0 that
+// k_batch_finalize sums after a reset.
 __global__ __launch_bounds__(kBatchThreads) void k_batch_finalize_col(const double *__restrict__ part1, int64_t n_blocks,
                                                                       int j, double *__restrict__ dc0,
                                                                       double *__restrict__ dc1, double *__restrict__ dcu,
                                                                       double *__restrict__ l1) {
-  __shared__ double red[kBatchThreads / kWave];
-  double acc = 0.0;
-  for (int64_t b = threadIdx.x; b < n_blocks; b += kBatchThreads) acc = __dadd_rn(acc, part1[b]);
-  acc = block_sum<kBatchThreads>(acc, red);
+  const double acc = one_col_total(part1, n_blocks);
   if (threadIdx.x == 0) {
     dc0[j] = acc;
     dc1[j] = acc;
@@ -737,7 +609,8 @@ struct BatchDeviceGuard {
   }
 };
 
-BatchArgs batch_args(const pr_batch *b) {
+// The iteration that reads the buffers of parity `cur`.
+BatchArgs batch_args(const pr_batch *b, int cur) {
   const pr_graph *g = b->g;
   BatchArgs a{};
   a.units = b->units.as<BatchUnit>();
@@ -746,11 +619,11 @@ BatchArgs batch_args(const pr_batch *b) {
   a.col = g->canon_col.as<int32_t>();
   a.deg = g->canon_deg.as<int32_t>();
   a.vflags = g->canon_vflags.as<uint8_t>();
-  a.cin = b->C[b->cur].as<double>();
-  a.cout = b->C[b->cur ^ 1].as<double>();
+  a.cin = b->C[cur].as<double>();
+  a.cout = b->C[cur ^ 1].as<double>();
   a.r = b->R.as<double>();
   a.t = b->T.as<double>();
-  a.dc = b->dc[b->cur].as<double>();
+  a.dc = b->dc[cur].as<double>();
   a.chunk_part = b->chunk_part.as<double>();
   a.part = b->part.as<double>();
   a.n_vertices = (double)b->V;
@@ -801,63 +674,37 @@ int ensure_ts(pr_batch *b) {
   return PR_OK;
 }
 
+// One iteration, reading the buffers of parity `cur`: the unit kernel, the long-row kernel, the
+// finalize step.  until: under the active mask (the host's b->cur then moves only once the executed
+// count is known), with a decide kernel at the end -- pr_batch_step_until_any's if `any`.  In
+// teleport mode the caller has brought ts up to date.
 template <int S>
-int launch_iteration(pr_batch *b) {
-  const BatchArgs a = batch_args(b);
-  if (teleport_mode(b)) {  // the caller has brought ts up to date
-    hipLaunchKernelGGL((k_batch_units_td<S, false>), dim3(b->ugrid), dim3(kWave), 0, b->stream, a, b->ts.as<double>(),
-                       (const BatchUntilState *)nullptr);
+int launch_iteration(pr_batch *b, int cur, bool until, double tol, bool any) {
+  const BatchArgs a = batch_args(b, cur);
+  const double *ts = b->ts.as<double>();
+  const BatchUntilState *us = until ? b->until.as<BatchUntilState>() : nullptr;
+  // a form's two kernels, with the arguments (`form`) that follow the common ones in both; the
+  // plain teleport form takes `us` too, nullptr as in every form that is not `until`
+  auto units_long = [&](auto units, auto long_rows, auto... form) -> int {
+    hipLaunchKernelGGL(units, dim3(b->ugrid), dim3(kWave), 0, b->stream, a, form...);
     PR_HIP(hipGetLastError());
     if (b->n_long > 0) {
-      hipLaunchKernelGGL((k_batch_long_td<S, false>), dim3(b->lgrid), dim3(kBatchThreads), 0, b->stream, a,
-                         b->long_row.as<int32_t>(), b->long_p0.as<int32_t>(), b->n_long, (int64_t)b->ugrid,
-                         b->ts.as<double>(), (const BatchUntilState *)nullptr);
+      hipLaunchKernelGGL(long_rows, dim3(b->lgrid), dim3(kBatchThreads), 0, b->stream, a, b->long_row.as<int32_t>(),
+                         b->long_p0.as<int32_t>(), b->n_long, (int64_t)b->ugrid, form...);
       PR_HIP(hipGetLastError());
     }
+    return PR_OK;
+  };
+  if (teleport_mode(b))
+    PR_TRY(until ? units_long(k_batch_units_td<S, true>, k_batch_long_td<S, true>, ts, us)
+                 : units_long(k_batch_units_td<S, false>, k_batch_long_td<S, false>, ts, us));
+  else if (until) PR_TRY(units_long(k_batch_units_until<S>, k_batch_long_until<S>, us));
+  else PR_TRY(units_long(k_batch_units<S>, k_batch_long<S>));
+  if (!until) {
     hipLaunchKernelGGL(k_batch_finalize, dim3(2 * S), dim3(kBatchThreads), 0, b->stream, b->part.as<double>(),
-                       (int64_t)b->ugrid + b->lgrid, S, b->dc[b->cur ^ 1].as<double>(), b->l1.as<double>());
+                       (int64_t)b->ugrid + b->lgrid, S, b->dc[cur ^ 1].as<double>(), b->l1.as<double>());
     PR_HIP(hipGetLastError());
     return PR_OK;
-  }
-  hipLaunchKernelGGL(k_batch_units<S>, dim3(b->ugrid), dim3(kWave), 0, b->stream, a);
-  PR_HIP(hipGetLastError());
-  if (b->n_long > 0) {
-    hipLaunchKernelGGL(k_batch_long<S>, dim3(b->lgrid), dim3(kBatchThreads), 0, b->stream, a, b->long_row.as<int32_t>(),
-                       b->long_p0.as<int32_t>(), b->n_long, (int64_t)b->ugrid);
-    PR_HIP(hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_batch_finalize, dim3(2 * S), dim3(kBatchThreads), 0, b->stream, b->part.as<double>(),
-                     (int64_t)b->ugrid + b->lgrid, S, b->dc[b->cur ^ 1].as<double>(), b->l1.as<double>());
-  PR_HIP(hipGetLastError());
-  return PR_OK;
-}
-
-// One iteration of pr_batch_step_until, reading the buffers of parity `cur` (the host's b->cur moves
-// only once the executed count is known).  any: the decision is pr_batch_step_until_any's.
-template <int S>
-int launch_iteration_until(pr_batch *b, int cur, double tol, bool any) {
-  BatchArgs a = batch_args(b);
-  a.cin = b->C[cur].as<double>();
-  a.cout = b->C[cur ^ 1].as<double>();
-  a.dc = b->dc[cur].as<double>();
-  const BatchUntilState *us = b->until.as<BatchUntilState>();
-  if (teleport_mode(b)) {  // the caller has brought ts up to date
-    hipLaunchKernelGGL((k_batch_units_td<S, true>), dim3(b->ugrid), dim3(kWave), 0, b->stream, a, b->ts.as<double>(), us);
-    PR_HIP(hipGetLastError());
-    if (b->n_long > 0) {
-      hipLaunchKernelGGL((k_batch_long_td<S, true>), dim3(b->lgrid), dim3(kBatchThreads), 0, b->stream, a,
-                         b->long_row.as<int32_t>(), b->long_p0.as<int32_t>(), b->n_long, (int64_t)b->ugrid,
-                         b->ts.as<double>(), us);
-      PR_HIP(hipGetLastError());
-    }
-  } else {
-    hipLaunchKernelGGL(k_batch_units_until<S>, dim3(b->ugrid), dim3(kWave), 0, b->stream, a, us);
-    PR_HIP(hipGetLastError());
-    if (b->n_long > 0) {
-      hipLaunchKernelGGL(k_batch_long_until<S>, dim3(b->lgrid), dim3(kBatchThreads), 0, b->stream, a,
-                         b->long_row.as<int32_t>(), b->long_p0.as<int32_t>(), b->n_long, (int64_t)b->ugrid, us);
-      PR_HIP(hipGetLastError());
-    }
   }
   hipLaunchKernelGGL(k_batch_finalize_until, dim3(2 * S), dim3(kBatchThreads), 0, b->stream, b->part.as<double>(),
                      (int64_t)b->ugrid + b->lgrid, S, b->dc[cur].as<double>(), b->dc[cur ^ 1].as<double>(),
@@ -924,6 +771,16 @@ int extract_column(pr_batch *b, int j) {
   return PR_OK;
 }
 
+// Column j of R, any column of the layout, to V doubles on the host; waited for.
+int download_ranks(pr_batch *b, int j, double *ranks_out) {
+  BatchDeviceGuard dg(b->device);
+  PR_TRY(extract_column(b, j));
+  if (b->V > 0)
+    PR_HIP(hipMemcpyAsync(ranks_out, b->colbuf.p, sizeof(double) * (size_t)b->V, hipMemcpyDeviceToHost, b->stream));
+  PR_HIP(hipStreamSynchronize(b->stream));
+  return PR_OK;
+}
+
 // extract_column for a column with an exclusion set: also fills excl_oid (allocated here).
 int extract_column_excl(pr_batch *b, int j) {
   if (!b->excl_oid.p) PR_TRY(b->excl_oid.alloc(sizeof(int32_t) * (size_t)std::max<int32_t>(b->V, 1)));
@@ -954,12 +811,48 @@ int topk_all(pr_batch *b, int32_t k, int64_t narrow_div, int32_t *ids_out, doubl
                       b->n_excl, k, narrow_div, ids_out, ranks_out, n_out, info);
 }
 
+bool bad_tol(double tol) { return !(tol >= 0.0) || std::isinf(tol); }
+
+// The loop of pr_batch_step_until and (any) pr_batch_step_until_any: starts the device's state from
+// `mask`, then enqueues up to `block` iterations at a time, up to max_iterations in all, and reads
+// the state back after each block -- into h_until, and h_queue if `any` -- until it says to stop: no
+// column active, or (any) a column converged.  The launches past the stopping iteration returned at
+// entry, so the batch's parity and count follow the device's executed count.  info (may be NULL):
+// iterations enqueued, iterations executed.
+int run_blocks(pr_batch *b, uint32_t mask, int32_t max_iterations, double tol, int32_t block, bool any, int32_t *info) {
+  BatchUntilState &h = b->h_until;
+  BatchQueueState &q = b->h_queue;
+  h = BatchUntilState{};
+  h.mask = mask;
+  PR_HIP(hipMemcpyAsync(b->until.p, &h, sizeof(h), hipMemcpyHostToDevice, b->stream));
+  if (any) {
+    q = BatchQueueState{0, 0};
+    PR_HIP(hipMemcpyAsync(b->qstate.p, &q, sizeof(q), hipMemcpyHostToDevice, b->stream));
+  }
+  int32_t enq = 0;
+  while (enq < max_iterations && (any ? q.saved == 0 : h.mask != 0)) {
+    const int32_t n = std::min(block, max_iterations - enq);
+    for (int32_t i = 0; i < n; ++i, ++enq) PR_TRY(PR_BATCH_DISPATCH(launch_iteration, b, b->cur ^ (enq & 1), true, tol, any));
+    // the one read-back per block: the mask, the executed count and the per-column counts
+    PR_HIP(hipMemcpyAsync(&h, b->until.p, sizeof(h), hipMemcpyDeviceToHost, b->stream));
+    if (any) PR_HIP(hipMemcpyAsync(&q, b->qstate.p, sizeof(q), hipMemcpyDeviceToHost, b->stream));
+    PR_HIP(hipStreamSynchronize(b->stream));
+  }
+  b->cur ^= h.executed & 1;
+  b->iters_done += h.executed;
+  if (info) {
+    info[0] = enq;
+    info[1] = h.executed;
+  }
+  return PR_OK;
+}
+
 // pr_batch_step_until with the block size as a parameter; info (may be NULL): iterations enqueued,
 // iterations executed.
 int step_until(pr_batch *b, int32_t max_iterations, double tol, int32_t block, int32_t *iters_out, int32_t *info) {
   if (!b) return fail(PR_ERR_INVALID, "NULL batch");
   if (max_iterations < 0) return fail(PR_ERR_INVALID, "max_iterations < 0");
-  if (!(tol >= 0.0) || std::isinf(tol)) return fail(PR_ERR_INVALID, "tol must be a finite number >= 0");
+  if (bad_tol(tol)) return fail(PR_ERR_INVALID, "tol must be a finite number >= 0");
   if (block < 1) return fail(PR_ERR_INVALID, "block < 1");
   if (b->in_done_cb) return fail(PR_ERR_STATE, kInDoneCb);
   if (!b->ready) return fail(PR_ERR_STATE, "pr_batch_step_until before pr_batch_reset");
@@ -970,27 +863,10 @@ int step_until(pr_batch *b, int32_t max_iterations, double tol, int32_t block, i
   }
   BatchDeviceGuard dg(b->device);
   if (teleport_mode(b)) PR_TRY(ensure_ts(b));
-  BatchUntilState &h = b->h_until;
-  h = BatchUntilState{};
-  h.mask = batch_until_all(b->width);
-  PR_HIP(hipMemcpyAsync(b->until.p, &h, sizeof(h), hipMemcpyHostToDevice, b->stream));
-  int32_t enq = 0;
-  while (enq < max_iterations && h.mask != 0) {
-    const int32_t n = std::min(block, max_iterations - enq);
-    for (int32_t i = 0; i < n; ++i, ++enq) PR_TRY(PR_BATCH_DISPATCH(launch_iteration_until, b, b->cur ^ (enq & 1), tol, false));
-    // the one read-back per block: the mask, the executed count and the per-column counts
-    PR_HIP(hipMemcpyAsync(&h, b->until.p, sizeof(h), hipMemcpyDeviceToHost, b->stream));
-    PR_HIP(hipStreamSynchronize(b->stream));
-  }
-  // the iterations past the last active column's returned at entry: parity and count follow the device
-  b->cur ^= h.executed & 1;
-  b->iters_done += h.executed;
+  PR_TRY(run_blocks(b, batch_until_all(b->width), max_iterations, tol, block, false, info));
+  const BatchUntilState &h = b->h_until;
   if (h.executed > 0) b->until_norms = true;
   if (iters_out) std::copy(h.iters, h.iters + b->width, iters_out);
-  if (info) {
-    info[0] = enq;
-    info[1] = h.executed;
-  }
   return PR_OK;
 }
 
@@ -1000,8 +876,6 @@ int check_column(const pr_batch *b, int32_t column) {
     return fail(PR_ERR_INVALID, "column " + std::to_string(column) + " is outside [0, width)");
   return PR_OK;
 }
-
-bool bad_tol(double tol) { return !(tol >= 0.0) || std::isinf(tol); }
 
 // pr_batch_step_until_any with the block size as a parameter; info (may be NULL): iterations
 // enqueued, iterations executed.
@@ -1028,30 +902,9 @@ int step_until_any(pr_batch *b, uint32_t active, int32_t max_iterations, double 
     PR_HIP(hipMemcpyAsync(b->dcu.p, used.p, sizeof(double) * b->stride, hipMemcpyDeviceToDevice, b->stream));
     b->until_norms = true;
   }
-  BatchUntilState &h = b->h_until;
-  BatchQueueState &q = b->h_queue;
-  h = BatchUntilState{};
-  h.mask = active;
-  q = BatchQueueState{0, 0};
-  PR_HIP(hipMemcpyAsync(b->until.p, &h, sizeof(h), hipMemcpyHostToDevice, b->stream));
-  PR_HIP(hipMemcpyAsync(b->qstate.p, &q, sizeof(q), hipMemcpyHostToDevice, b->stream));
-  int32_t enq = 0;
-  while (enq < max_iterations && q.saved == 0) {
-    const int32_t n = std::min(block, max_iterations - enq);
-    for (int32_t i = 0; i < n; ++i, ++enq) PR_TRY(PR_BATCH_DISPATCH(launch_iteration_until, b, b->cur ^ (enq & 1), tol, true));
-    PR_HIP(hipMemcpyAsync(&h, b->until.p, sizeof(h), hipMemcpyDeviceToHost, b->stream));
-    PR_HIP(hipMemcpyAsync(&q, b->qstate.p, sizeof(q), hipMemcpyDeviceToHost, b->stream));
-    PR_HIP(hipStreamSynchronize(b->stream));
-  }
-  // the launches past the stopping iteration returned at entry: parity and count follow the device
-  b->cur ^= h.executed & 1;
-  b->iters_done += h.executed;
-  *executed_out = h.executed;
-  *converged_out = q.converged;
-  if (info) {
-    info[0] = enq;
-    info[1] = h.executed;
-  }
+  PR_TRY(run_blocks(b, active, max_iterations, tol, block, true, info));
+  *executed_out = b->h_until.executed;
+  *converged_out = b->h_queue.converged;
   return PR_OK;
 }
 
@@ -1337,7 +1190,7 @@ int pr_batch_step(pr_batch *b, int32_t iterations) {
     b->until_norms = false;  // every column advances: the last iteration's dc is dc[cur ^ 1] again
   }
   for (int32_t it = 0; it < iterations; ++it) {
-    PR_TRY(PR_BATCH_DISPATCH(pr::launch_iteration, b));
+    PR_TRY(PR_BATCH_DISPATCH(pr::launch_iteration, b, b->cur, false, 0.0, false));
     b->cur ^= 1;
     ++b->iters_done;
   }
@@ -1436,12 +1289,7 @@ int pr_batch_get_ranks(pr_batch *b, int32_t column, double *ranks_out) {
   PR_TRY(pr::check_column(b, column));
   if (!ranks_out) return fail(PR_ERR_INVALID, "NULL argument");
   if (!b->ready) return fail(PR_ERR_STATE, "pr_batch_get_ranks before pr_batch_reset");
-  pr::BatchDeviceGuard dg(b->device);
-  PR_TRY(pr::extract_column(b, column));
-  if (b->V > 0)
-    PR_HIP(hipMemcpyAsync(ranks_out, b->colbuf.p, sizeof(double) * (size_t)b->V, hipMemcpyDeviceToHost, b->stream));
-  PR_HIP(hipStreamSynchronize(b->stream));
-  return PR_OK;
+  return pr::download_ranks(b, column, ranks_out);
 }
 
 // Internal entry point (not part of include/pagerank_hip.h): pr_batch_get_ranks for any column of the
@@ -1451,12 +1299,7 @@ int pr_batch_get_ranks_ex(pr_batch *b, int32_t column, double *ranks_out) {
   if (column < 0 || column >= b->stride) return fail(PR_ERR_INVALID, "column is outside [0, stride)");
   if (b->in_done_cb) return fail(PR_ERR_STATE, pr::kInDoneCb);
   if (!b->ready) return fail(PR_ERR_STATE, "pr_batch_get_ranks_ex before pr_batch_reset");
-  pr::BatchDeviceGuard dg(b->device);
-  PR_TRY(pr::extract_column(b, column));
-  if (b->V > 0)
-    PR_HIP(hipMemcpyAsync(ranks_out, b->colbuf.p, sizeof(double) * (size_t)b->V, hipMemcpyDeviceToHost, b->stream));
-  PR_HIP(hipStreamSynchronize(b->stream));
-  return PR_OK;
+  return pr::download_ranks(b, column, ranks_out);
 }
 
 int pr_batch_get_norms(pr_batch *b, double *dc_out, double *l_out) {

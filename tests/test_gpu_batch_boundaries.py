@@ -195,7 +195,7 @@ def test_boundary_rows_dangling_none(hip, oracle_c):
         case.close()
 
 
-@pytest.mark.parametrize("width", [3, 16])
+@pytest.mark.parametrize("width", [1, 2, 3, 5, 16])
 def test_until_siblings_at_boundaries(hip, boundary, width):
     case, cols = boundary, list(range(width))
     b, model, terms = open_batch(hip, case, width)
@@ -207,10 +207,10 @@ def test_until_siblings_at_boundaries(hip, boundary, width):
         iters = b.step_until(3, 0.0)
         assert iters.tolist() == [3] * width
         assert_same(want, all_bits(b, cols), "step_until(3, 0.0) against step(3)")
-        # the odd columns advance, the even ones are frozen: one iteration per call, so that norms()
-        # describes it
-        active = [j for j in cols if j % 2 == 1]
-        still = [j for j in cols if j % 2 == 0]
+        # the odd columns advance, the even ones are frozen (at width 1 the single column advances and
+        # nothing is frozen): one iteration per call, so that norms() describes it
+        active = [j for j in cols if j % 2 == 1] if width > 1 else [0]
+        still = [j for j in cols if j not in active]
         mask = sum(1 << j for j in active)
 
         def advance():

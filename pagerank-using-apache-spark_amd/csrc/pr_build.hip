@@ -7,8 +7,12 @@
 //   count()                  (:162)      -> N = n_vertices (all interned IDs must appear)
 //   dangUrls fixup           (:172-184)  -> D = sink-only vertices, resolved here once
 // then lays the part's rows out for the iteration (pr_graph.h) and plans the SpMV work units.
+//
+// The kernels come first, then the stages -- each a function of what it reads, returning what it
+// produces -- and last build_graph, the driver, from which every temporary's lifetime can be read.
+// The decisions that fix a graph's shape (layout, classes, geometry, entry code, hot-set size) are
+// the pure functions of pr_layout.h.
 #include <algorithm>
-#include <cstdlib>
 #include <chrono>
 #include <vector>
 
@@ -21,6 +25,28 @@ namespace pr {
 namespace {
 
 constexpr uint64_t kSentinel = ~0ull;
+constexpr unsigned kT = 256;  // workgroup size of the build's grid-stride kernels
+using ull = unsigned long long;  // the counters kernels add to
+
+// ---- host helpers of the stages -----------------------------------------------------------
+// Copies n items to the host and waits for the stream.
+template <class T> int fetch(T *dst, const DevBuf &src, size_t n, hipStream_t s) {
+  if (n) PR_HIP(hipMemcpyAsync(dst, src.p, sizeof(T) * n, hipMemcpyDeviceToHost, s));
+  PR_HIP(hipStreamSynchronize(s));
+  return PR_OK;
+}
+// Allocates v.size() + extra items and uploads v, which must outlive the stream's next wait.
+template <class T> int upload(DevBuf *d, const std::vector<T> &v, size_t extra, hipStream_t s) {
+  PR_TRY(d->alloc(sizeof(T) * (v.size() + extra)));
+  if (!v.empty()) PR_HIP(hipMemcpyAsync(d->p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, s));
+  return PR_OK;
+}
+// Allocates zeroed bytes: flags, and the counters a kernel adds to (read back with fetch).
+int zeroed(DevBuf *d, size_t bytes, hipStream_t s) {
+  PR_TRY(d->alloc(bytes));
+  PR_HIP(hipMemsetAsync(d->p, 0, bytes, s));
+  return PR_OK;
+}
 
 // ---- validation + key packing ----------------------------------------------------------
 __global__ void k_pack_edges(int64_t E, int32_t V, int b, const int32_t *__restrict__ src,
@@ -219,24 +245,20 @@ __global__ void k_local_rows(int64_t R, int64_t n_local, int P, int part, ClassG
   }
 }
 
-
-}  // namespace
-
-// Greedy work plan over the part's row_ptr (host; linear, deterministic).
-void plan_units(const std::vector<int64_t> &rp, int unit_nnz, int unit_rows, UnitPlan *plan,
-                int64_t row_begin, int64_t row_end, bool append) {
-  const int64_t R = row_end < 0 ? (int64_t)rp.size() - 1 : row_end;
-  if (!append) {
-    plan->units.clear();
-    plan->src_off.clear();
-    plan->lr_row.clear();
-    plan->lr_p0.clear();
-    plan->n_pieces = 0;
-    plan->padded_len = 0;
-  } else if (!plan->lr_p0.empty()) {
-    plan->lr_p0.pop_back();  // re-appended at the end
-  }
-  int64_t pieces = plan->n_pieces, pad = plan->padded_len, v = row_begin;
+// Host plan of the fused layout over a part's row_ptr: units, their source offsets in the unpadded
+// column array, long rows (split into pieces) and the padded column length.
+struct UnitPlan {
+  std::vector<Unit> units;
+  std::vector<int64_t> src_off;  // per unit: first in-link in the unpadded CSR
+  std::vector<int32_t> lr_row, lr_p0;
+  int64_t n_pieces = 0;
+  int64_t padded_len = 0;
+};
+// Greedy, linear, deterministic.
+void plan_units(const std::vector<int64_t> &rp, int unit_nnz, int unit_rows, UnitPlan *plan) {
+  const int64_t R = (int64_t)rp.size() - 1;
+  *plan = UnitPlan{};
+  int64_t pieces = 0, pad = 0, v = 0;
   auto push = [&](int64_t src, int32_t r0, int32_t meta, int32_t n) {
     plan->units.push_back(Unit{(uint32_t)(pad / 8), r0, meta, n});
     plan->src_off.push_back(src);
@@ -271,7 +293,6 @@ void plan_units(const std::vector<int64_t> &rp, int unit_nnz, int unit_rows, Uni
   plan->padded_len = pad;
 }
 
-namespace {
 __global__ void k_pad_cols(const Unit *__restrict__ units, const int64_t *__restrict__ src_off,
                            const int32_t *__restrict__ col, int32_t *__restrict__ colp) {
   const Unit u = units[blockIdx.x];
@@ -279,23 +300,21 @@ __global__ void k_pad_cols(const Unit *__restrict__ units, const int64_t *__rest
   const int n = unit_n(u);
   for (int i = threadIdx.x; i < n; i += blockDim.x) colp[d + i] = col[s + i];
 }
-}  // namespace
-
+// colp[8*p8 + i] = col[src_off + i] for every unit (padding entries are 0).
 int build_padded_cols(const UnitPlan &plan, const int32_t *col, int32_t *colp, hipStream_t s) {
   const size_t nu = plan.units.size();
   PR_HIP(hipMemsetAsync(colp, 0, sizeof(int32_t) * (plan.padded_len > 0 ? plan.padded_len : 1), s));
   if (nu == 0) return PR_OK;
   DevBuf du, ds;
-  PR_TRY(du.alloc(sizeof(Unit) * nu));
-  PR_TRY(ds.alloc(sizeof(int64_t) * nu));
-  PR_HIP(hipMemcpyAsync(du.p, plan.units.data(), sizeof(Unit) * nu, hipMemcpyHostToDevice, s));
-  PR_HIP(hipMemcpyAsync(ds.p, plan.src_off.data(), sizeof(int64_t) * nu, hipMemcpyHostToDevice, s));
+  PR_TRY(upload(&du, plan.units, 0, s));
+  PR_TRY(upload(&ds, plan.src_off, 0, s));
   hipLaunchKernelGGL(k_pad_cols, dim3((unsigned)nu), dim3(256), 0, s, du.as<Unit>(), ds.as<int64_t>(),
                      col, colp);
   PR_HIP(hipGetLastError());
   PR_HIP(hipStreamSynchronize(s));
   return PR_OK;
 }
+}  // namespace
 
 // ---- split layout: entry codes (pr_internal.h, pr_spmv.h k_spmv_hot) -----------------------
 // Entry code (pr_internal.h); a segment end is marked in bit 0 (codes are byte offsets /
@@ -511,478 +530,448 @@ struct PiecePlan {
   std::vector<int32_t> pc, tbl;
   int64_t vmax = 0;
 };
-static int plan_pieces(const pr_graph *g, const int32_t *cmap, int C, int P, PiecePlan *pp, hipStream_t s) {
+
+// ---- the build's stages (build_graph below is their driver) -------------------------------------
+namespace {
+int plan_pieces(const pr_graph *g, const int32_t *cmap, PiecePlan *pp) {
   DevBuf lohi;
-  const int64_t np = (int64_t)C * P;
+  const int64_t np = (int64_t)g->C * g->nparts;
   PR_TRY(lohi.alloc(sizeof(int32_t) * 2 * (size_t)np));
-  hipLaunchKernelGGL(k_piece_bounds, dim3((unsigned)np), dim3(256), 0, s, g->S_pad, g->Q_pad, C, P, cmap,
-                     lohi.as<int32_t>(), lohi.as<int32_t>() + np);
+  hipLaunchKernelGGL(k_piece_bounds, dim3((unsigned)np), dim3(256), 0, g->stream, g->S_pad, g->Q_pad, g->C, g->nparts,
+                     cmap, lohi.as<int32_t>(), lohi.as<int32_t>() + np);
   PR_HIP(hipGetLastError());
   std::vector<int32_t> h((size_t)(2 * np));
-  PR_HIP(hipMemcpyAsync(h.data(), lohi.p, sizeof(int32_t) * h.size(), hipMemcpyDeviceToHost, s));
-  PR_HIP(hipStreamSynchronize(s));
-  pp->vmax = piece_tables(h.data(), C, P, &pp->pc, &pp->tbl);  // pr_pieces.h
+  PR_TRY(fetch(h.data(), lohi, h.size(), g->stream));
+  pp->vmax = piece_tables(h.data(), g->C, g->nparts, &pp->pc, &pp->tbl);  // pr_pieces.h
   return PR_OK;
 }
 
-// Column classes of the split layout: the fewest (8, 16, 32, 64) whose class region of the part's
-// gather space (its slice plus the expected received runs at P > 1) fits one XCD's 4 MiB L2 (the
-// phased schedule runs one class per XCD at a time), capped at kAutoMaxClasses; PR_BOPT_CLASSES
-// overrides.  More classes keep more gathers in L2 and the LDS hot sets but cost epilogue work per
-// (row, class): R-MAT s26 (262 MB) -> 64 at P = 1, 2, 4 and 32 for an 8-way part (121 MB: 8 % less
-// per iteration than 64); the Twitter shape stays at 64 at P = 8 (6 % better than 32); ER s24
-// (134 MB) -> 64, LiveJournal (39 MB) -> 16 (profiles/r02/class_policy/).
-constexpr int64_t kClassRegionBytes = 4000000;  // just under the 4 MiB L2: ER s24 (4.19 MB at 32) stays at 64
-static int class_setting(const pr_build_opts &o, int64_t gather_bytes) {
-  if (o.classes) return o.classes;
-  for (int c = kXcds; c < kAutoMaxClasses; c *= 2)
-    if (gather_bytes <= (int64_t)c * kClassRegionBytes) return c;
-  return kAutoMaxClasses;
-}
-
-static int hot_slots_setting(const pr_build_opts &o) {
-  const int k = o.hot_slots < 0 ? kHotSlotsDefault : o.hot_slots;
-  return std::max(0, std::min(k, kHotSlotsMax));
-}
-
-int build_graph(pr_graph *g, int64_t E, const int32_t *src_in, const int32_t *dst_in) {
-  static_assert(kMaxClasses == 16 * kXcds, "class counts");
-  auto t_start = std::chrono::steady_clock::now();
+// Inputs and validation: uploads the edge list unless PR_INPUT_DEVICE, packs every edge into a
+// sort key (dst << b | src; kSentinel for a record without links) and checks the IDs.
+// Out: keys (E of them), is_key[v] = v is the source of a record.
+int pack_inputs(pr_graph *g, int64_t E, const int32_t *src, const int32_t *dst, int b, DevBuf *keys, DevBuf *is_key) {
   hipStream_t s = g->stream;
   const int32_t V = g->V;
-  const int P = g->nparts, part = g->part;
-  if (V < 0 || E < 0) return fail(PR_ERR_INVALID, "negative n_vertices or n_edges");
-  if (E >= (int64_t(1) << 32) - 1) return fail(PR_ERR_INVALID, "n_edges must be < 2^32 - 1");
-  const int b = bits_for((uint64_t)V);  // every ID < 2^b - 1: sentinel sorts last
-  const unsigned T = 256;
-
-  // ---- inputs on the device ----
-  DevBuf dsrc, ddst;
-  const int32_t *src = src_in, *dst = dst_in;
+  DevBuf dsrc, ddst, appear, err;
   if (!(g->flags & PR_INPUT_DEVICE) && E > 0) {
     PR_TRY(dsrc.alloc(sizeof(int32_t) * E));
     PR_TRY(ddst.alloc(sizeof(int32_t) * E));
-    PR_HIP(hipMemcpyAsync(dsrc.p, src_in, sizeof(int32_t) * E, hipMemcpyHostToDevice, s));
-    PR_HIP(hipMemcpyAsync(ddst.p, dst_in, sizeof(int32_t) * E, hipMemcpyHostToDevice, s));
+    PR_HIP(hipMemcpyAsync(dsrc.p, src, sizeof(int32_t) * E, hipMemcpyHostToDevice, s));
+    PR_HIP(hipMemcpyAsync(ddst.p, dst, sizeof(int32_t) * E, hipMemcpyHostToDevice, s));
     src = dsrc.as<int32_t>();
     dst = ddst.as<int32_t>();
   }
-
-  DevBuf keys, tmp, appear, is_key, err, cnt;
-  const int64_t Ealloc = E > 0 ? E : 1;
-  PR_TRY(keys.alloc(sizeof(uint64_t) * Ealloc));
-  PR_TRY(tmp.alloc(sizeof(uint64_t) * Ealloc));
-  PR_TRY(appear.alloc((size_t)V + 1));
-  PR_TRY(is_key.alloc((size_t)V + 1));
-  PR_TRY(err.alloc(sizeof(unsigned)));
-  PR_TRY(cnt.alloc(sizeof(unsigned long long) * 8));
-  PR_HIP(hipMemsetAsync(appear.p, 0, (size_t)V + 1, s));
-  PR_HIP(hipMemsetAsync(is_key.p, 0, (size_t)V + 1, s));
-  PR_HIP(hipMemsetAsync(err.p, 0, sizeof(unsigned), s));
-  PR_HIP(hipMemsetAsync(cnt.p, 0, sizeof(unsigned long long) * 8, s));
+  PR_TRY(keys->alloc(sizeof(uint64_t) * (E > 0 ? E : 1)));
+  PR_TRY(zeroed(&appear, (size_t)V + 1, s));
+  PR_TRY(zeroed(is_key, (size_t)V + 1, s));
+  PR_TRY(zeroed(&err, sizeof(unsigned), s));
   if (E > 0)
-    hipLaunchKernelGGL(k_pack_edges, dim3(grid_for(E, T, 65536)), dim3(T), 0, s, E, V, b, src, dst,
-                       keys.as<uint64_t>(), appear.as<uint8_t>(), is_key.as<uint8_t>(),
-                       err.as<unsigned>());
+    hipLaunchKernelGGL(k_pack_edges, dim3(grid_for(E, kT, 65536)), dim3(kT), 0, s, E, V, b, src, dst,
+                       keys->as<uint64_t>(), appear.as<uint8_t>(), is_key->as<uint8_t>(), err.as<unsigned>());
   if (V > 0)
-    hipLaunchKernelGGL(k_check_appear, dim3(grid_for(V, T, 65536)), dim3(T), 0, s, V,
-                       appear.as<uint8_t>(), err.as<unsigned>());
+    hipLaunchKernelGGL(k_check_appear, dim3(grid_for(V, kT, 65536)), dim3(kT), 0, s, V, appear.as<uint8_t>(),
+                       err.as<unsigned>());
   PR_HIP(hipGetLastError());
   unsigned herr = 0;
-  PR_HIP(hipMemcpyAsync(&herr, err.p, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-  PR_HIP(hipStreamSynchronize(s));
-  dsrc.reset();
-  ddst.reset();
-  appear.reset();
+  PR_TRY(fetch(&herr, err, 1, s));
   if (herr & 1u) return fail(PR_ERR_INVALID, "edge list holds an ID outside [0, n_vertices) (dst may be -1)");
   if (herr & 2u) return fail(PR_ERR_INVALID, "an ID in [0, n_vertices) never appears in the edge list");
+  return PR_OK;
+}
 
-  // ---- A1: sort + dedupe (Sparky.java:124) ----
-  PR_TRY(radix_sort_u64(keys.as<uint64_t>(), tmp.as<uint64_t>(), E, 0, 2 * b, s));
-  int64_t m = 0;
-  PR_TRY(compact_index(E, UniquePred{keys.as<uint64_t>()}, IdentityU64{keys.as<uint64_t>()},
-                       tmp.as<uint64_t>(), &m, s));
-  g->E_dedup = m;
-  uint64_t *ukeys = tmp.as<uint64_t>();
-  const uint64_t maskb = (uint64_t(1) << b) - 1;
+// A1, sort + dedupe (Sparky.java:124).  Out: ukeys, the m distinct edges in key order (g->E_dedup);
+// keys is scratch from here on.
+int sort_dedupe(pr_graph *g, int64_t E, int b, DevBuf *keys, DevBuf *ukeys, int64_t *m) {
+  PR_TRY(ukeys->alloc(sizeof(uint64_t) * (E > 0 ? E : 1)));
+  PR_TRY(radix_sort_u64(keys->as<uint64_t>(), ukeys->as<uint64_t>(), E, 0, 2 * b, g->stream));
+  PR_TRY(compact_index(E, UniquePred{keys->as<uint64_t>()}, IdentityU64{keys->as<uint64_t>()},
+                       ukeys->as<uint64_t>(), m, g->stream));
+  g->E_dedup = *m;
+  return PR_OK;
+}
 
-  // ---- canonical CSR, degrees, flags ----
-  DevBuf c_rowptr, c_col, c_deg, c_vflags;
-  PR_TRY(c_rowptr.alloc(sizeof(int64_t) * ((size_t)V + 1)));
-  PR_TRY(c_col.alloc(sizeof(int32_t) * (m > 0 ? m : 1)));
-  PR_TRY(c_deg.alloc(sizeof(int32_t) * ((size_t)V + 1)));
-  PR_TRY(c_vflags.alloc((size_t)V + 1));
-  PR_HIP(hipMemsetAsync(c_deg.p, 0, sizeof(int32_t) * ((size_t)V + 1), s));
-  hipLaunchKernelGGL(k_row_ptr, dim3(grid_for(m + 1, T, 65536)), dim3(T), 0, s, ukeys, m, b,
-                     (int64_t)V, c_rowptr.as<int64_t>());
+// Canonical CSR in original IDs, out-degrees and vertex flags, with the graph's counters
+// (g->n_sink, n_nolink, n_indeg0, max_indeg) and the largest out-degree.
+struct Canon {
+  DevBuf rowptr, col, deg, vflags;
+  uint64_t max_outdeg = 0;
+};
+int canonical_csr(pr_graph *g, const uint64_t *ukeys, int64_t m, int b, const DevBuf &is_key, Canon *c) {
+  hipStream_t s = g->stream;
+  const int32_t V = g->V;
+  DevBuf cnt;  // k_vflags: {n_sink, n_nolink, n_indeg0, max_indeg, max_outdeg}
+  PR_TRY(zeroed(&cnt, 5 * sizeof(ull), s));
+  PR_TRY(c->rowptr.alloc(sizeof(int64_t) * ((size_t)V + 1)));
+  PR_TRY(c->col.alloc(sizeof(int32_t) * (m > 0 ? m : 1)));
+  PR_TRY(zeroed(&c->deg, sizeof(int32_t) * ((size_t)V + 1), s));
+  PR_TRY(c->vflags.alloc((size_t)V + 1));
+  hipLaunchKernelGGL(k_row_ptr, dim3(grid_for(m + 1, kT, 65536)), dim3(kT), 0, s, ukeys, m, b, (int64_t)V,
+                     c->rowptr.as<int64_t>());
   if (m > 0)
-    hipLaunchKernelGGL(k_canon_col_deg, dim3(grid_for(m, T, 65536)), dim3(T), 0, s, ukeys, m, maskb,
-                       c_col.as<int32_t>(), c_deg.as<int32_t>());
+    hipLaunchKernelGGL(k_canon_col_deg, dim3(grid_for(m, kT, 65536)), dim3(kT), 0, s, ukeys, m,
+                       (uint64_t(1) << b) - 1, c->col.as<int32_t>(), c->deg.as<int32_t>());
   if (V > 0)
-    hipLaunchKernelGGL(k_vflags, dim3(grid_for(V, T, 4096)), dim3(T), 0, s, V, is_key.as<uint8_t>(),
-                       c_deg.as<int32_t>(), c_rowptr.as<int64_t>(), c_vflags.as<uint8_t>(),
-                       cnt.as<unsigned long long>());
+    hipLaunchKernelGGL(k_vflags, dim3(grid_for(V, kT, 4096)), dim3(kT), 0, s, V, is_key.as<uint8_t>(),
+                       c->deg.as<int32_t>(), c->rowptr.as<int64_t>(), c->vflags.as<uint8_t>(), cnt.as<ull>());
   PR_HIP(hipGetLastError());
-  unsigned long long hc[8] = {0};
-  PR_HIP(hipMemcpyAsync(hc, cnt.p, sizeof(hc), hipMemcpyDeviceToHost, s));
-  PR_HIP(hipStreamSynchronize(s));
-  is_key.reset();
+  ull hc[5] = {0};
+  PR_TRY(fetch(hc, cnt, 5, s));
   g->n_sink = (int64_t)hc[0];
   g->n_nolink = (int64_t)hc[1];
   g->n_indeg0 = (int64_t)hc[2];
   g->max_indeg = (int64_t)hc[3];
-  const uint64_t max_outdeg = hc[4];
+  c->max_outdeg = hc[4];
+  return PR_OK;
+}
 
-  // ---- internal order: out-degree desc, ID asc (hot contributions first) ----
+// Internal order (out-degree desc, ID asc: hot contributions first), the layout decision
+// (pr_layout.h) and the geometry that follows from it: g->n_local*, gather_est, layout, C, Q_pad,
+// n_rows, S_pad, geo, nblk.  Out: the sorted order keys, and per vertex its sorted index and the
+// gather position of its contribution.
+struct Order { DevBuf vk, rank_of, gpos; };
+int order_and_geometry(pr_graph *g, int b, const Canon &cn, Order *o) {
+  hipStream_t s = g->stream;
+  const int32_t V = g->V;
+  const int P = g->nparts, part = g->part;
   g->n_local_max = (V + P - 1) / P;
   g->n_local = V > part ? (V - part + P - 1) / P : 0;
-  if (max_outdeg > kRowDegMask) return fail(PR_ERR_INVALID, "out-degree above 2^28-1 is not supported");
-  // Column classes when the gather space (every part's slice: the columns a part reads) outgrows
-  // the L2s (pr_graph.h); their count from the part's expected compacted gather space.
-  int64_t gather_est = g->n_local_max * 8;
+  if (cn.max_outdeg > kRowDegMask) return fail(PR_ERR_INVALID, "out-degree above 2^28-1 is not supported");
+  // the class count comes from the part's expected compacted gather space: its slice plus, at
+  // P > 1, the peers' sources it is expected to read
+  g->gather_est = g->n_local_max * 8;
   if (P > 1 && V > 0) {
-    PR_HIP(hipMemsetAsync(cnt.p, 0, sizeof(unsigned long long), s));
-    hipLaunchKernelGGL(k_reader_est, dim3(grid_for(V, T, 1024)), dim3(T), 0, s, V, P, c_deg.as<int32_t>(),
-                       cnt.as<unsigned long long>());
+    DevBuf sum;
+    PR_TRY(zeroed(&sum, sizeof(ull), s));
+    hipLaunchKernelGGL(k_reader_est, dim3(grid_for(V, kT, 1024)), dim3(kT), 0, s, V, P, cn.deg.as<int32_t>(), sum.as<ull>());
     PR_HIP(hipGetLastError());
-    unsigned long long est = 0;
-    PR_HIP(hipMemcpyAsync(&est, cnt.p, sizeof(est), hipMemcpyDeviceToHost, s));
-    PR_HIP(hipStreamSynchronize(s));
-    gather_est += (int64_t)((double)est / 1048576.0 * (double)(P - 1) / (double)P) * 8;
+    ull est = 0;
+    PR_TRY(fetch(&est, sum, 1, s));
+    g->gather_est += (int64_t)((double)est / 1048576.0 * (double)(P - 1) / (double)P) * 8;
   }
-  g->gather_est = gather_est;
-  const int bd = bits_for(max_outdeg);
-  const uint64_t maxd = (uint64_t(1) << bd) - 1;
-  DevBuf vk, vtmp, rank_of, gpos;
-  PR_TRY(vk.alloc(sizeof(uint64_t) * ((size_t)V + 1)));
+  const int bd = bits_for(cn.max_outdeg);
+  DevBuf vtmp;
+  PR_TRY(o->vk.alloc(sizeof(uint64_t) * ((size_t)V + 1)));
   PR_TRY(vtmp.alloc(sizeof(uint64_t) * ((size_t)V + 1)));
-  PR_TRY(rank_of.alloc(sizeof(int32_t) * ((size_t)V + 1)));
-  PR_TRY(gpos.alloc(sizeof(int32_t) * ((size_t)V + 1)));
+  PR_TRY(o->rank_of.alloc(sizeof(int32_t) * ((size_t)V + 1)));
+  PR_TRY(o->gpos.alloc(sizeof(int32_t) * ((size_t)V + 1)));
   if (V > 0) {
-    hipLaunchKernelGGL(k_order_keys, dim3(grid_for(V, T, 4096)), dim3(T), 0, s, V, b, maxd, c_deg.as<int32_t>(),
-                       vk.as<uint64_t>());
-    PR_TRY(radix_sort_u64(vk.as<uint64_t>(), vtmp.as<uint64_t>(), V, 0, b + bd, s));
+    hipLaunchKernelGGL(k_order_keys, dim3(grid_for(V, kT, 4096)), dim3(kT), 0, s, V, b, (uint64_t(1) << bd) - 1,
+                       cn.deg.as<int32_t>(), o->vk.as<uint64_t>());
+    PR_TRY(radix_sort_u64(o->vk.as<uint64_t>(), vtmp.as<uint64_t>(), V, 0, b + bd, s));
   }
   vtmp.reset();
-  // Layout policy: the fused layout while the gather space fits the L2s, the split layout beyond
-  // (profiles/r03/rows_layout/: a row-block layout with LDS row sums and no partial slots ran 2x
-  // slower at ER s24 and far slower on skewed graphs, and was removed)
-  const int c_split = class_setting(g->opts, gather_est);
-  const bool big = (int64_t)P * g->n_local_max * 8 > kSplitMinSliceBytes;
-  int layout = big ? kLayoutSplit : kLayoutFused;
-  if (g->flags & PR_LAYOUT_FUSED) layout = kLayoutFused;
-  if (g->flags & PR_LAYOUT_SPLIT) layout = kLayoutSplit;
-  // split-layout entry codes are byte offsets below 2^31 (pr_internal.h)
-  if ((int64_t)P * (g->n_local_max + 64 + kMaxClasses) * 8 >= (1ll << 31) - (1ll << 20)) layout = kLayoutFused;
-  int C = layout == kLayoutSplit ? c_split : 1;
-  g->layout = layout;
-  g->C = C;
-  g->Q_pad = (g->n_local_max + C - 1) / C;
-  g->Q_pad = (g->Q_pad + 63) / 64 * 64;  // rows come in whole 64-row blocks (k_epilogue_grp)
-  g->n_rows = (int64_t)C * g->Q_pad;
-  g->S_pad = ((g->n_rows + 2 + 63) / 64) * 64;
-  if ((int64_t)P * g->S_pad >= (int64_t(1) << 31)) return fail(PR_ERR_INVALID, "gather space exceeds 2^31 entries");
+  const LayoutGeom l = choose_layout(g->flags, g->opts.classes, P, g->n_local_max, g->gather_est);
+  if (!l.fits) return fail(PR_ERR_INVALID, "gather space exceeds 2^31 entries");
+  g->layout = l.layout;
+  g->C = l.C;
+  g->Q_pad = l.Q_pad;
+  g->n_rows = l.n_rows;
+  g->S_pad = l.S_pad;
+  g->geo = ClassGeom{l.C, l.Q_pad, l.S_pad};
+  g->nblk = (l.n_rows + 63) / 64;
   if (V > 0) {
-    hipLaunchKernelGGL(k_rank_gpos, dim3(grid_for(V, T, 65536)), dim3(T), 0, s, V, maskb, P, C,
-                       g->Q_pad, g->S_pad, vk.as<uint64_t>(), rank_of.as<int32_t>(), gpos.as<int32_t>());
+    hipLaunchKernelGGL(k_rank_gpos, dim3(grid_for(V, kT, 65536)), dim3(kT), 0, s, V, (uint64_t(1) << b) - 1, P, l.C,
+                       l.Q_pad, l.S_pad, o->vk.as<uint64_t>(), o->rank_of.as<int32_t>(), o->gpos.as<int32_t>());
     PR_HIP(hipGetLastError());
   }
-  ClassGeom geo{};
-  geo.C = C;
-  geo.Q_pad = g->Q_pad;
-  geo.S_pad = g->S_pad;
-  g->geo = geo;
+  return PR_OK;
+}
 
-  // ---- exchange lists (P > 1): which of this part's contributions every peer reads ----
-  DevBuf cmap;  // global -> compacted gather position (P > 1, sparse exchange)
-  PR_TRY(build_exchange(g, ukeys, m, b, maskb, rank_of.as<int32_t>(), gpos.as<int32_t>(), &cmap));
-
-  // ---- the part's in-link CSRs: one per column class (one in the fused layout) ----
+// The part's local keys: its in-links as (class of the source, local row, gather position of the
+// source) in bg + brow + class bits, sorted.  Out: keys (g->local_nnz of them), g->col (gather
+// positions, mapped into the compacted gather space when there is a cmap), g->rowinfo and orig
+// (local row -> original ID).  ukeys is the sort's scratch from here on.
+int local_keys(pr_graph *g, int64_t m, int b, int bg, int brow, const Canon &cn, const Order &o, const DevBuf &cmap,
+               DevBuf *ukeys, DevBuf *keys, DevBuf *orig) {
+  hipStream_t s = g->stream;
+  const int P = g->nparts, part = g->part;
   const int64_t R = g->n_rows;
-  const int bg = bits_for((uint64_t)P * g->S_pad);
-  const int brow = bits_for((uint64_t)R);
-  const int bseg = bits_for((uint64_t)C);
-  const uint64_t maskg = (uint64_t(1) << bg) - 1;
+  const uint64_t maskb = (uint64_t(1) << b) - 1;
   int64_t lm = 0;
-  PR_TRY(compact_index(m, PartPred{ukeys, rank_of.as<int32_t>(), b, P, part},
-                       PartXform{ukeys, gpos.as<int32_t>(), b, bg, brow, maskb, geo},
-                       keys.as<uint64_t>(), &lm, s));
+  PR_TRY(compact_index(m, PartPred{ukeys->as<uint64_t>(), o.rank_of.as<int32_t>(), b, P, part},
+                       PartXform{ukeys->as<uint64_t>(), o.gpos.as<int32_t>(), b, bg, brow, maskb, g->geo},
+                       keys->as<uint64_t>(), &lm, s));
   g->local_nnz = lm;
-  PR_TRY(radix_sort_u64(keys.as<uint64_t>(), tmp.as<uint64_t>(), lm, 0, bg + brow + bseg, s));
+  PR_TRY(radix_sort_u64(keys->as<uint64_t>(), ukeys->as<uint64_t>(), lm, 0, bg + brow + bits_for((uint64_t)g->C), s));
   PR_TRY(g->col.alloc(sizeof(int32_t) * (lm > 0 ? lm : 1)));
   if (lm > 0)
-    hipLaunchKernelGGL(k_local_col, dim3(grid_for(lm, T, 65536)), dim3(T), 0, s,
-                       keys.as<uint64_t>(), lm, maskg, g->col.as<int32_t>());
+    hipLaunchKernelGGL(k_local_col, dim3(grid_for(lm, kT, 65536)), dim3(kT), 0, s, keys->as<uint64_t>(), lm,
+                       (uint64_t(1) << bg) - 1, g->col.as<int32_t>());
   if (cmap.p && lm > 0) {  // columns -> the compacted gather space (order within rows kept)
     DevBuf bad;
-    PR_TRY(bad.alloc(sizeof(unsigned long long)));
-    PR_HIP(hipMemsetAsync(bad.p, 0, sizeof(unsigned long long), s));
-    hipLaunchKernelGGL(k_map_cols, dim3(grid_for(lm, T, 65536)), dim3(T), 0, s, lm, cmap.as<int32_t>(),
-                       g->col.as<int32_t>(), bad.as<unsigned long long>());
-    unsigned long long hb = 0;
-    PR_HIP(hipMemcpyAsync(&hb, bad.p, sizeof(hb), hipMemcpyDeviceToHost, s));
-    PR_HIP(hipStreamSynchronize(s));
+    PR_TRY(zeroed(&bad, sizeof(ull), s));
+    hipLaunchKernelGGL(k_map_cols, dim3(grid_for(lm, kT, 65536)), dim3(kT), 0, s, lm, cmap.as<int32_t>(),
+                       g->col.as<int32_t>(), bad.as<ull>());
+    ull hb = 0;
+    PR_TRY(fetch(&hb, bad, 1, s));
     if (hb) return fail(PR_ERR_STATE, "exchange lists miss a source of this part's in-links");
   }
   PR_TRY(g->rowinfo.alloc(sizeof(uint32_t) * ((size_t)R + 1)));
-  DevBuf orig;
-  PR_TRY(orig.alloc(sizeof(int32_t) * ((size_t)R + 1)));
-  hipLaunchKernelGGL(k_local_rows, dim3(grid_for(R, T, 65536)), dim3(T), 0, s, R, g->n_local, P, part,
-                     geo, maskb, (g->flags & PR_DANGLING_NONE) != 0, vk.as<uint64_t>(),
-                     c_deg.as<int32_t>(), c_vflags.as<uint8_t>(), g->rowinfo.as<uint32_t>(),
-                     orig.as<int32_t>());
+  PR_TRY(orig->alloc(sizeof(int32_t) * ((size_t)R + 1)));
+  hipLaunchKernelGGL(k_local_rows, dim3(grid_for(R, kT, 65536)), dim3(kT), 0, s, R, g->n_local, P, part, g->geo, maskb,
+                     (g->flags & PR_DANGLING_NONE) != 0, o.vk.as<uint64_t>(), cn.deg.as<int32_t>(),
+                     cn.vflags.as<uint8_t>(), g->rowinfo.as<uint32_t>(), orig->as<int32_t>());
   PR_HIP(hipGetLastError());
-  vk.reset();
-  rank_of.reset();
-  gpos.reset();
+  return PR_OK;
+}
 
-  // ---- work plans (fused: host greedy over the row pointers; split: pr_plan.hip on the GPU) ----
-  const uint64_t rmask = (uint64_t(1) << brow) - 1;
-  std::vector<int64_t> rp;
-  std::vector<int32_t> seg_p0;
-  std::vector<int32_t> lr_row, lr_p0;
-  std::vector<Unit> light_units;
-  int64_t pieces = 0;
-  g->nblk = (R + 63) / 64;
-  std::vector<int64_t> poff(kMaxClasses + 1, 0);
-  if (C == 1) {
-    // fused layout: one CSR over all rows, 256-thread units with the fused epilogue
-    DevBuf rp_dev;
-    PR_TRY(rp_dev.alloc(sizeof(int64_t) * ((size_t)R + 1)));
-    hipLaunchKernelGGL(k_row_ptr_seg, dim3(grid_for(lm + 1, T, 65536)), dim3(T), 0, s, keys.as<uint64_t>(),
-                       (int64_t)0, lm, bg, rmask, R, rp_dev.as<int64_t>());
-    PR_HIP(hipGetLastError());
-    rp.assign((size_t)R + 1, 0);
-    PR_HIP(hipMemcpyAsync(rp.data(), rp_dev.p, sizeof(int64_t) * rp.size(), hipMemcpyDeviceToHost, s));
-    PR_HIP(hipStreamSynchronize(s));
-    keys.reset();
-    tmp.reset();
-    UnitPlan px;
-    plan_units(rp, kUnitNnz, kUnitRows, &px);
-    g->rowptr = std::move(rp_dev);
-    lr_row = px.lr_row;
-    lr_p0 = px.lr_p0;
-    light_units = px.units;
-    pieces = px.n_pieces;
-    if (px.padded_len / 8 >= (int64_t(1) << 32)) return fail(PR_ERR_INVALID, "graph part too large for 32-bit unit offsets");
-    PR_TRY(g->colp.alloc(sizeof(int32_t) * (px.padded_len > 0 ? px.padded_len : 8)));
-    PR_TRY(build_padded_cols(px, g->col.as<int32_t>(), g->colp.as<int32_t>(), s));
-    seg_p0.push_back(0);
-  } else {
-    // split layout: segments (row, class), class masks, block bases and wave units, planned on
-    // the GPU (pr_plan.hip); the slot of segment k is k, so the class boundaries are poff
-    SplitPlanner sp;
-    PR_TRY(sp.segments(keys.as<uint64_t>(), lm, bg, brow, C, R, g->col.as<int32_t>(), s));
-    keys.reset();
-    tmp.reset();
-    for (int x = 0; x <= C; ++x) poff[x] = sp.cseg[x];
-    for (int x = C; x < kMaxClasses; ++x) poff[x + 1] = poff[x];
-    for (int x = 0; x < C; ++x)
-      if (poff[x + 1] - poff[x] >= (int64_t(1) << 29)) return fail(PR_ERR_INVALID, "a column class exceeds 2^29 segments");
-    // k_epilogue_grp addresses partials through int32 absolute slot indices (< 2^31 slots: R-MAT
-    // s26 has ~2^28.1, the Twitter shape ~2^29; a graph several times their size still fits)
-    if (poff[C] >= (int64_t(1) << 31) - 4) return fail(PR_ERR_INVALID, "more than 2^31 - 4 partial slots");
-    // per-block first slots (absolute), plus the sentinel block row of every class's end slot
-    PR_TRY(sp.block_bases(true, s));
-    PR_TRY(sp.units_plan(s));
-    g->rmask = std::move(sp.rmask);
-    g->cbase = std::move(sp.cbase);
-    PR_TRY(plan_epi_walk(g));
-    pieces = sp.n_pieces;
-    if (sp.entries / 8 >= (int64_t(1) << 32)) return fail(PR_ERR_INVALID, "graph part too large for 32-bit unit offsets");
-    // LDS hot set per class, then the entry codes
-    // entry codes: compact when every region index fits (P = 1: a class's sources are its region
-    // of the one slice; 2.5 bytes per entry below 2^19 region rows, 3 below 2^20); a part of a row
-    // partition takes the piece codes when its classes' virtual spaces fit (the hot set then gives
-    // its last kPieceTblSlots slots to the piece table), else 32-bit codes
-    int slots = hot_slots_setting(g->opts);
-    const bool compact = g->opts.codes != 0 && P == 1 && g->gsize == g->S_pad;
-    g->code = compact && g->Q_pad < (int64_t(1) << kC20IdxBits)   ? kCodeC20
-              : compact && g->Q_pad < (int64_t(1) << kC24IdxBits) ? kCodeC24
-                                                                   : kCodeU32;
-    PiecePlan pplan;
-    if (g->opts.codes != 0 && P > 1 && P <= kMaxPackParts) {
-      PR_TRY(plan_pieces(g, cmap.p ? cmap.as<int32_t>() : nullptr, C, P, &pplan, s));
-      HotGeom t{};
-      t.P = P;
-      t.tbl = 1;
-      int ps = slots;
-      for (;; --ps) {  // the largest hot set that leaves LDS room for the table
-        t.Kp = ps / P;
-        if (t.lds_bytes() <= (size_t)kHotLdsBytes) break;
-      }
-      const int64_t top = (int64_t)P * (ps / P) + pplan.vmax;  // largest idx + 1
-      g->code = top < (int64_t(1) << kC20IdxBits)   ? kCodeC20P
-                : top < (int64_t(1) << kC24IdxBits) ? kCodeC24P
-                                                     : kCodeU32;
-      if (code_is_piece(g->code)) slots = ps;
-    }
-    HotGeom hg{};
-    hg.C = C;
-    hg.P = P;
-    hg.Kp = slots / P;
-    hg.q_load = (int)std::min<int64_t>(hg.Kp, g->Q_pad);
-    hg.S_pad = g->S_pad;
-    hg.Q_pad = g->Q_pad;
-    hg.tbl = code_is_piece(g->code) ? 1 : 0;
-    g->hot = hg;
-    // hot-set gather positions per class, and the LDS slot of every hot gather position
-    DevBuf hotidx;
-    const int64_t nh = (int64_t)P * hg.Kp;
-    PR_TRY(g->hpos.alloc(sizeof(int32_t) * (size_t)(C * nh > 0 ? C * nh : 1)));
-    PR_TRY(hotidx.alloc(sizeof(int32_t) * (size_t)g->gsize));
-    PR_HIP(hipMemsetAsync(hotidx.p, 0, sizeof(int32_t) * (size_t)g->gsize, s));
-    if (C * nh > 0)
-      hipLaunchKernelGGL(k_hot_tables, dim3(grid_for(C * nh, T, 65536)), dim3(T), 0, s, hg,
-                         cmap.p ? cmap.as<int32_t>() : nullptr, g->hpos.as<int32_t>(), hotidx.as<int32_t>());
-    PR_HIP(hipGetLastError());
-    int n_cu = 0;
-    PR_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, g->device));
-    g->hot_grid = std::max(C, n_cu / C * C);  // C | grid: every class gets the same CUs
-    g->hot_grid_full = g->hot_grid;
-    PR_TRY(set_hot_reserve(g, g->opts.hot_reserve));
+// Both layouts' plans end alike: the host copy of orig, whose wait also covers the plan's uploads.
+int rows_to_host(pr_graph *g, const DevBuf &orig) {
+  g->orig_of_local.resize((size_t)g->n_rows);
+  return fetch(g->orig_of_local.data(), orig, (size_t)g->n_rows, g->stream);
+}
 
-    PR_TRY(prepare_hot_kernel());
-    const int64_t nu = sp.n_units;
-    g->n_hunits = nu;
-    g->hunits = std::move(sp.units);  // + the empty unit nu
-    PR_TRY(g->hucum.alloc(sizeof(int64_t) * (kMaxClasses + 1)));
-    PR_TRY(g->poff.alloc(sizeof(int64_t) * (kMaxClasses + 1)));
-    const bool c20 = g->code == kCodeC20 || g->code == kCodeC20P, c24 = g->code == kCodeC24 || g->code == kCodeC24P;
-    const bool piece = code_is_piece(g->code);
-    if (piece) {
-      PR_TRY(g->ptab.alloc(sizeof(int32_t) * pplan.tbl.size()));
-      PR_HIP(hipMemcpyAsync(g->ptab.p, pplan.tbl.data(), sizeof(int32_t) * pplan.tbl.size(), hipMemcpyHostToDevice, s));
-    }
-    DevBuf pcd;
-    if (piece) {
-      PR_TRY(pcd.alloc(sizeof(int32_t) * pplan.pc.size()));
-      PR_HIP(hipMemcpyAsync(pcd.p, pplan.pc.data(), sizeof(int32_t) * pplan.pc.size(), hipMemcpyHostToDevice, s));
-    }
-    if (c20 || c24) {
-      PR_TRY(g->colh.alloc(sizeof(uint16_t) * (sp.entries > 0 ? sp.entries : 8)));
-      PR_TRY(g->cside.alloc((c24 ? sizeof(uint64_t) : sizeof(uint32_t)) * (sp.entries > 0 ? sp.entries / 8 : 1)));
-    } else {
-      PR_TRY(g->colh.alloc(sizeof(uint32_t) * (sp.entries > 0 ? sp.entries : 8)));
-      PR_TRY(g->cside.alloc(sizeof(uint32_t)));
-    }
-    // + 2 slots: the grouped epilogue stages class runs in 16-byte pairs (one slot past the end)
-    PR_TRY(g->partial.alloc(sizeof(double) * (size_t)(poff[C] + 2)));
-    g->n_slots = poff[C];
-    PR_HIP(hipMemcpyAsync(g->hucum.p, sp.ucum.data(), sizeof(int64_t) * (kMaxClasses + 1), hipMemcpyHostToDevice, s));
-    PR_HIP(hipMemcpyAsync(g->poff.p, poff.data(), sizeof(int64_t) * (kMaxClasses + 1), hipMemcpyHostToDevice, s));
-    if (nu > 0) {
-      PR_HIP(hipMemsetAsync(cnt.p, 0, 2 * sizeof(unsigned long long), s));
-      const unsigned fgrid = (unsigned)std::min<int64_t>(nu, 65536);
-      const int nhs = P * hg.Kp;
-      if (piece && c20)
-        hipLaunchKernelGGL((k_fill_piece<3, uint32_t>), dim3(fgrid), dim3(64), 0, s, nu, g->hunits.as<Unit>(),
-                           sp.src_off.as<int64_t>(), sp.n_real.as<int32_t>(), g->col.as<int32_t>(),
-                           g->hucum.as<int64_t>(), C, P, pcd.as<int32_t>(), hotidx.as<int32_t>(), nhs,
-                           g->colh.as<uint16_t>(), g->cside.as<uint32_t>(), cnt.as<unsigned long long>(),
-                           cnt.as<unsigned long long>() + 1);
-      else if (piece)
-        hipLaunchKernelGGL((k_fill_piece<4, uint64_t>), dim3(fgrid), dim3(64), 0, s, nu, g->hunits.as<Unit>(),
-                           sp.src_off.as<int64_t>(), sp.n_real.as<int32_t>(), g->col.as<int32_t>(),
-                           g->hucum.as<int64_t>(), C, P, pcd.as<int32_t>(), hotidx.as<int32_t>(), nhs,
-                           g->colh.as<uint16_t>(), g->cside.as<uint64_t>(), cnt.as<unsigned long long>(),
-                           cnt.as<unsigned long long>() + 1);
-      else if (c20)
-        hipLaunchKernelGGL((k_fill_compact<3, uint32_t>), dim3((unsigned)std::min<int64_t>(nu, 65536)), dim3(64), 0, s,
-                           nu, g->hunits.as<Unit>(), sp.src_off.as<int64_t>(), sp.n_real.as<int32_t>(),
-                           g->col.as<int32_t>(), g->Q_pad, hg.q_load, g->colh.as<uint16_t>(),
-                           g->cside.as<uint32_t>(), cnt.as<unsigned long long>(), cnt.as<unsigned long long>() + 1);
-      else if (c24)
-        hipLaunchKernelGGL((k_fill_compact<4, uint64_t>), dim3((unsigned)std::min<int64_t>(nu, 65536)), dim3(64), 0, s,
-                           nu, g->hunits.as<Unit>(), sp.src_off.as<int64_t>(), sp.n_real.as<int32_t>(),
-                           g->col.as<int32_t>(), g->Q_pad, hg.q_load, g->colh.as<uint16_t>(),
-                           g->cside.as<uint64_t>(), cnt.as<unsigned long long>(), cnt.as<unsigned long long>() + 1);
-      else
-        hipLaunchKernelGGL(k_fill_hot, dim3((unsigned)std::min<int64_t>(nu, 65536)), dim3(256), 0, s, nu,
-                           g->hunits.as<Unit>(), sp.src_off.as<int64_t>(), sp.n_real.as<int32_t>(),
-                           g->col.as<int32_t>(), hotidx.as<int32_t>(), g->colh.as<uint32_t>(),
-                           cnt.as<unsigned long long>());
-      PR_HIP(hipGetLastError());
-      unsigned long long n_hot[2] = {0, 0};
-      PR_HIP(hipMemcpyAsync(n_hot, cnt.p, sizeof(n_hot), hipMemcpyDeviceToHost, s));
-      PR_HIP(hipStreamSynchronize(s));
-      if (n_hot[1]) return fail(PR_ERR_STATE, "compact codes: a unit reads outside its class region / pieces");
-      g->hot_cover_ppm = lm > 0 ? (int64_t)((double)n_hot[0] * 1e6 / (double)lm) : 0;
-    }
-    g->n_segs = sp.n_long;
-    g->seg_slot = std::move(sp.seg_slot);
-    g->seg_p0 = std::move(sp.seg_p0);
-  }
+// Fused layout: one CSR over all rows (g->rowptr, g->colp), a greedy host plan of 256-thread units
+// with the fused epilogue (g->units, lr_row, lr_p0, piece_part; no long segments: seg_slot and
+// seg_p0 hold one entry).  Frees keys and scratch after the row pointers, g->col after the columns.
+int plan_fused(pr_graph *g, int bg, int brow, DevBuf *keys, DevBuf *scratch, const DevBuf &orig) {
+  hipStream_t s = g->stream;
+  const int64_t R = g->n_rows, lm = g->local_nnz;
+  PR_TRY(g->rowptr.alloc(sizeof(int64_t) * ((size_t)R + 1)));
+  hipLaunchKernelGGL(k_row_ptr_seg, dim3(grid_for(lm + 1, kT, 65536)), dim3(kT), 0, s, keys->as<uint64_t>(), (int64_t)0,
+                     lm, bg, (uint64_t(1) << brow) - 1, R, g->rowptr.as<int64_t>());
+  PR_HIP(hipGetLastError());
+  std::vector<int64_t> rp((size_t)R + 1, 0);
+  PR_TRY(fetch(rp.data(), g->rowptr, rp.size(), s));
+  keys->reset();
+  scratch->reset();
+  UnitPlan px;
+  plan_units(rp, kUnitNnz, kUnitRows, &px);
+  if (px.padded_len / 8 >= (int64_t(1) << 32)) return fail(PR_ERR_INVALID, "graph part too large for 32-bit unit offsets");
+  PR_TRY(g->colp.alloc(sizeof(int32_t) * (px.padded_len > 0 ? px.padded_len : 8)));
+  PR_TRY(build_padded_cols(px, g->col.as<int32_t>(), g->colp.as<int32_t>(), s));
   g->col.reset();
-  if (lr_p0.empty()) lr_p0.push_back((int32_t)pieces);
-  g->n_units = (int64_t)light_units.size();
-  g->n_long = (int64_t)lr_row.size();
-  g->n_pieces = pieces;
-  PR_TRY(g->units.alloc(sizeof(Unit) * (light_units.size() + 1)));
-  PR_TRY(g->lr_row.alloc(sizeof(int32_t) * (lr_row.size() + 1)));
-  PR_TRY(g->lr_p0.alloc(sizeof(int32_t) * (lr_p0.size() + 1)));
-  if (C == 1) {  // no long segments (the split planner filled these)
-    g->n_segs = 0;
-    PR_TRY(g->seg_slot.alloc(sizeof(int64_t)));
-    PR_TRY(g->seg_p0.alloc(sizeof(int32_t) * (seg_p0.size() + 1)));
-    PR_HIP(hipMemcpyAsync(g->seg_p0.p, seg_p0.data(), sizeof(int32_t) * seg_p0.size(), hipMemcpyHostToDevice, s));
-  }
+  g->n_units = (int64_t)px.units.size();
+  g->n_long = (int64_t)px.lr_row.size();
+  g->n_pieces = px.n_pieces;
+  g->n_segs = 0;
+  const std::vector<int32_t> seg_p0{0};
+  PR_TRY(g->seg_slot.alloc(sizeof(int64_t)));
+  PR_TRY(upload(&g->seg_p0, seg_p0, 1, s));
   PR_TRY(g->piece_part.alloc(sizeof(double) * ((size_t)g->n_pieces + 1)));
-  if (!light_units.empty())
-    PR_HIP(hipMemcpyAsync(g->units.p, light_units.data(), sizeof(Unit) * light_units.size(), hipMemcpyHostToDevice, s));
-  if (!lr_row.empty())
-    PR_HIP(hipMemcpyAsync(g->lr_row.p, lr_row.data(), sizeof(int32_t) * lr_row.size(), hipMemcpyHostToDevice, s));
-  PR_HIP(hipMemcpyAsync(g->lr_p0.p, lr_p0.data(), sizeof(int32_t) * lr_p0.size(), hipMemcpyHostToDevice, s));
-  g->orig_of_local.resize((size_t)R);
-  if (R > 0)
-    PR_HIP(hipMemcpyAsync(g->orig_of_local.data(), orig.p, sizeof(int32_t) * R, hipMemcpyDeviceToHost, s));
-  PR_HIP(hipStreamSynchronize(s));
+  PR_TRY(upload(&g->units, px.units, 1, s));
+  PR_TRY(upload(&g->lr_row, px.lr_row, 1, s));
+  PR_TRY(upload(&g->lr_p0, px.lr_p0, 1, s));
+  return rows_to_host(g, orig);
+}
 
-  // ---- iteration state ----
-  PR_TRY(g->r.alloc(sizeof(double) * ((size_t)g->n_rows + 1)));
-  for (int k = 0; k < 2; ++k) {
-    PR_TRY(g->cbuf[k].alloc(sizeof(double) * (size_t)g->gsize));
-    PR_HIP(hipMemsetAsync(g->cbuf[k].p, 0, sizeof(double) * (size_t)g->gsize, s));
+// Entry code and hot set of a split part (pr_layout.h): g->code and g->hot; *pp the piece plan when
+// the part may take piece codes (the hot set then gives its last kPieceTblSlots slots to the table).
+int choose_codes(pr_graph *g, const int32_t *cmap, PiecePlan *pp) {
+  const int P = g->nparts;
+  CodeChoice cc{code_one_part(g->opts.codes, P, g->gsize == g->S_pad, g->Q_pad), hot_slots_setting(g->opts.hot_slots)};
+  if (piece_codes_allowed(g->opts.codes, P)) {
+    PR_TRY(plan_pieces(g, cmap, pp));
+    cc = code_of_parts(cc.slots, P, pp->vmax);
   }
+  g->code = cc.code;
+  const int Kp = cc.slots / P, q_load = (int)std::min<int64_t>(Kp, g->Q_pad);
+  g->hot = HotGeom{g->C, P, Kp, q_load, g->S_pad, g->Q_pad, code_is_piece(cc.code) ? 1 : 0};
+  return PR_OK;
+}
+
+// Hot-set gather positions per class (g->hpos) and the LDS slot of every hot gather position
+// (*hotidx, 0: cold), then the grid of k_spmv_hot.
+int hot_tables(pr_graph *g, const int32_t *cmap, DevBuf *hotidx) {
+  hipStream_t s = g->stream;
+  const int C = g->C;
+  const int64_t nh = (int64_t)g->nparts * g->hot.Kp;
+  PR_TRY(g->hpos.alloc(sizeof(int32_t) * (size_t)(C * nh > 0 ? C * nh : 1)));
+  PR_TRY(zeroed(hotidx, sizeof(int32_t) * (size_t)g->gsize, s));
+  if (C * nh > 0)
+    hipLaunchKernelGGL(k_hot_tables, dim3(grid_for(C * nh, kT, 65536)), dim3(kT), 0, s, g->hot, cmap,
+                       g->hpos.as<int32_t>(), hotidx->as<int32_t>());
+  PR_HIP(hipGetLastError());
+  int n_cu = 0;
+  PR_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, g->device));
+  g->hot_grid = std::max(C, n_cu / C * C);  // C | grid: every class gets the same CUs
+  g->hot_grid_full = g->hot_grid;
+  PR_TRY(set_hot_reserve(g, g->opts.hot_reserve));
+  return prepare_hot_kernel();
+}
+
+// Writes the entry codes of the planner's wave units in g->code's format (g->colh, g->cside) and
+// sets g->hot_cover_ppm; pcd: the piece plan's {g0, g1, v0} (piece codes only).
+int fill_codes(pr_graph *g, const SplitPlanner &sp, const DevBuf &pcd, const DevBuf &hotidx) {
+  hipStream_t s = g->stream;
+  const int64_t nu = sp.n_units;
+  DevBuf cnt;  // {entries that read the LDS hot set, sources outside the unit's class}
+  PR_TRY(zeroed(&cnt, 2 * sizeof(ull), s));
+  ull *n_hot = cnt.as<ull>(), *bad = n_hot + 1;
+  auto run = [&](auto kernel, unsigned threads, auto... rest) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)std::min<int64_t>(nu, 65536)), dim3(threads), 0, s, nu,
+                       g->hunits.as<Unit>(), sp.src_off.as<int64_t>(), sp.n_real.as<int32_t>(), g->col.as<int32_t>(),
+                       rest...);
+  };
+  auto piece = [&](auto kernel, auto *side) {
+    run(kernel, 64u, g->hucum.as<int64_t>(), g->C, g->nparts, pcd.as<int32_t>(), hotidx.as<int32_t>(),
+        g->nparts * g->hot.Kp, g->colh.as<uint16_t>(), side, n_hot, bad);
+  };
+  auto compact = [&](auto kernel, auto *side) {
+    run(kernel, 64u, g->Q_pad, g->hot.q_load, g->colh.as<uint16_t>(), side, n_hot, bad);
+  };
+  switch (g->code) {
+    case kCodeC20P: piece(k_fill_piece<3, uint32_t>, g->cside.as<uint32_t>()); break;
+    case kCodeC24P: piece(k_fill_piece<4, uint64_t>, g->cside.as<uint64_t>()); break;
+    case kCodeC20: compact(k_fill_compact<3, uint32_t>, g->cside.as<uint32_t>()); break;
+    case kCodeC24: compact(k_fill_compact<4, uint64_t>, g->cside.as<uint64_t>()); break;
+    default: run(k_fill_hot, 256u, hotidx.as<int32_t>(), g->colh.as<uint32_t>(), n_hot);
+  }
+  PR_HIP(hipGetLastError());
+  ull n[2] = {0, 0};
+  PR_TRY(fetch(n, cnt, 2, s));
+  if (n[1]) return fail(PR_ERR_STATE, "compact codes: a unit reads outside its class region / pieces");
+  g->hot_cover_ppm = g->local_nnz > 0 ? (int64_t)((double)n[0] * 1e6 / (double)g->local_nnz) : 0;
+  return PR_OK;
+}
+
+// Split layout: segments (row, class), class masks, block bases and wave units, planned on the GPU
+// (pr_plan.hip; the slot of segment k is k, so the class boundaries are poff), the LDS hot set per
+// class and the entry codes.  Sets every split field of g, and the fused fields to empty.  Frees
+// keys and scratch after segments(), g->col after the codes.
+int plan_split(pr_graph *g, int bg, int brow, const DevBuf &cmap_buf, DevBuf *keys, DevBuf *scratch,
+               const DevBuf &orig) {
+  hipStream_t s = g->stream;
+  const int C = g->C;
+  const int32_t *cmap = cmap_buf.p ? cmap_buf.as<int32_t>() : nullptr;
+  SplitPlanner sp;
+  PR_TRY(sp.segments(keys->as<uint64_t>(), g->local_nnz, bg, brow, C, g->n_rows, g->col.as<int32_t>(), s));
+  keys->reset();
+  scratch->reset();
+  std::vector<int64_t> poff(kMaxClasses + 1, 0);
+  for (int x = 0; x <= C; ++x) poff[x] = sp.cseg[x];
+  for (int x = C; x < kMaxClasses; ++x) poff[x + 1] = poff[x];
+  for (int x = 0; x < C; ++x)
+    if (poff[x + 1] - poff[x] >= (int64_t(1) << 29)) return fail(PR_ERR_INVALID, "a column class exceeds 2^29 segments");
+  // k_epilogue_grp addresses partials through int32 absolute slot indices (< 2^31 slots: R-MAT
+  // s26 has ~2^28.1, the Twitter shape ~2^29; a graph several times their size still fits)
+  if (poff[C] >= (int64_t(1) << 31) - 4) return fail(PR_ERR_INVALID, "more than 2^31 - 4 partial slots");
+  // per-block first slots (absolute), plus the sentinel block row of every class's end slot
+  PR_TRY(sp.block_bases(true, s));
+  PR_TRY(sp.units_plan(s));
+  g->rmask = std::move(sp.rmask);
+  g->cbase = std::move(sp.cbase);
+  PR_TRY(plan_epi_walk(g));
+  if (sp.entries / 8 >= (int64_t(1) << 32)) return fail(PR_ERR_INVALID, "graph part too large for 32-bit unit offsets");
+  PiecePlan pplan;
+  PR_TRY(choose_codes(g, cmap, &pplan));
+  DevBuf hotidx, pcd;
+  PR_TRY(hot_tables(g, cmap, &hotidx));
+  g->n_hunits = sp.n_units;
+  g->hunits = std::move(sp.units);  // + the empty unit n_units
+  if (code_is_piece(g->code)) {
+    PR_TRY(upload(&g->ptab, pplan.tbl, 0, s));
+    PR_TRY(upload(&pcd, pplan.pc, 0, s));
+  }
+  const int64_t ne = sp.entries;
+  if (g->code == kCodeU32) {
+    PR_TRY(g->colh.alloc(sizeof(uint32_t) * (ne > 0 ? ne : 8)));
+    PR_TRY(g->cside.alloc(sizeof(uint32_t)));
+  } else {  // u16 low halves, and per 8 entries a side word: u32 (C20 codes) or u64 (C24)
+    const bool c24 = g->code == kCodeC24 || g->code == kCodeC24P;
+    PR_TRY(g->colh.alloc(sizeof(uint16_t) * (ne > 0 ? ne : 8)));
+    PR_TRY(g->cside.alloc((c24 ? sizeof(uint64_t) : sizeof(uint32_t)) * (ne > 0 ? ne / 8 : 1)));
+  }
+  // + 2 slots: the grouped epilogue stages class runs in 16-byte pairs (one slot past the end)
+  PR_TRY(g->partial.alloc(sizeof(double) * (size_t)(poff[C] + 2)));
+  g->n_slots = poff[C];
+  PR_TRY(upload(&g->hucum, sp.ucum, 0, s));
+  PR_TRY(upload(&g->poff, poff, 0, s));
+  if (sp.n_units > 0) PR_TRY(fill_codes(g, sp, pcd, hotidx));
+  g->col.reset();
+  g->n_segs = sp.n_long;
+  g->seg_slot = std::move(sp.seg_slot);
+  g->seg_p0 = std::move(sp.seg_p0);
+  // no fused units or long rows: lr_p0 holds the piece count alone
+  g->n_units = g->n_long = 0;
+  g->n_pieces = sp.n_pieces;
+  const std::vector<int32_t> lr_p0{(int32_t)sp.n_pieces};
+  PR_TRY(g->units.alloc(sizeof(Unit)));
+  PR_TRY(g->lr_row.alloc(sizeof(int32_t)));
+  PR_TRY(upload(&g->lr_p0, lr_p0, 1, s));
+  PR_TRY(g->piece_part.alloc(sizeof(double) * ((size_t)g->n_pieces + 1)));
+  return rows_to_host(g, orig);
+}
+
+// Iteration state: ranks, the double-buffered gather space, the finalize, reset and epilogue grids
+// and their partials.
+int iteration_state(pr_graph *g) {
+  hipStream_t s = g->stream;
+  const int C = g->C;
+  PR_TRY(g->r.alloc(sizeof(double) * ((size_t)g->n_rows + 1)));
+  for (int k = 0; k < 2; ++k) PR_TRY(zeroed(&g->cbuf[k], sizeof(double) * (size_t)g->gsize, s));
   // k_finalize: one wave per long row, at least 16 workgroups (4096 threads for the block
   // partials), at most 512
   g->fin_blocks = (int)std::min<int64_t>(512, std::max<int64_t>(16, (g->n_long + kThreads / kWave - 1) / (kThreads / kWave)));
   PR_TRY(g->fin_part.alloc(sizeof(double) * 2 * g->fin_blocks));
-  PR_TRY(g->fin_counter.alloc(sizeof(unsigned) * 4));
-  PR_HIP(hipMemsetAsync(g->fin_counter.p, 0, sizeof(unsigned) * 4, s));
+  PR_TRY(zeroed(&g->fin_counter, sizeof(unsigned) * 4, s));
   g->reset_blocks = (int)grid_for(g->n_rows > 0 ? g->n_rows : 1, 256, 2048);
+  // the split epilogue writes one {dangling, L1} partial per group (pr_spmv.h epi_group)
+  const int64_t ngrp = C > 1 ? (g->nblk + kEpiGroup - 1) / kEpiGroup : 0;
   if (C > 1) {
     // one wave per group, no grid cap: the whole grid in one dispatch lets the workgroups of the
     // last round finish together (R-MAT s26: 16 K workgroups, -1.8 % per step against a 2048 cap
     // whose waves stride over 8 groups; profiles/r02/experiments.md).  One-wave workgroups pay off
     // when many groups walk (a cheap group's wave frees its LDS window at once: R-MAT s26 -0.8 %),
     // four-wave ones on uniform graphs (ER s24 +1.3 % narrow); at most 64 classes
-    const int64_t ngrp = (g->nblk + kEpiGroup - 1) / kEpiGroup;
     const bool auto_narrow = g->n_walk_groups * 10 >= ngrp;
     g->epi_narrow = epi_narrow_ok(C) && (g->opts.epi_narrow < 0 ? auto_narrow : g->opts.epi_narrow != 0);
     g->ep_blocks = (int)grid_for(ngrp, epi_grp_threads(g->epi_narrow) / kWave, 1u << 20);
     PR_TRY(plan_epi_order(g));
   }
-  // the split epilogue writes one {dangling, L1} partial per group (pr_spmv.h epi_group)
-  const int64_t ep_parts = C > 1 ? (g->nblk + kEpiGroup - 1) / kEpiGroup : 0;
   // finalize input: fused-unit partials (C = 1) or the split epilogue's group partials (C > 1)
-  PR_TRY(g->unit_part.alloc(sizeof(double) * 2 * ((size_t)g->n_units + ep_parts + 1)));
+  PR_TRY(g->unit_part.alloc(sizeof(double) * 2 * ((size_t)g->n_units + ngrp + 1)));
   PR_TRY(g->reset_part.alloc(sizeof(double) * 2 * g->reset_blocks));
+  return PR_OK;
+}
 
-  if (g->flags & PR_NO_CANONICAL) {
-    c_rowptr.reset();
-    c_col.reset();
-    c_deg.reset();
-    c_vflags.reset();
-    g->has_canonical = false;
-  } else {
-    g->canon_rowptr = std::move(c_rowptr);
-    g->canon_col = std::move(c_col);
-    g->canon_deg = std::move(c_deg);
-    g->canon_vflags = std::move(c_vflags);
-    g->has_canonical = true;
+// The canonical CSR goes to the handle, or away under PR_NO_CANONICAL.
+void keep_canonical(pr_graph *g, Canon *c) {
+  g->has_canonical = !(g->flags & PR_NO_CANONICAL);
+  if (!g->has_canonical) {
+    *c = Canon{};
+    return;
   }
-  PR_HIP(hipStreamSynchronize(s));
+  g->canon_rowptr = std::move(c->rowptr);
+  g->canon_col = std::move(c->col);
+  g->canon_deg = std::move(c->deg);
+  g->canon_vflags = std::move(c->vflags);
+}
+}  // namespace
+
+int build_graph(pr_graph *g, int64_t E, const int32_t *src, const int32_t *dst) {
+  auto t_start = std::chrono::steady_clock::now();
+  const int32_t V = g->V;
+  if (V < 0 || E < 0) return fail(PR_ERR_INVALID, "negative n_vertices or n_edges");
+  if (E >= (int64_t(1) << 32) - 1) return fail(PR_ERR_INVALID, "n_edges must be < 2^32 - 1");
+  const int b = bits_for((uint64_t)V);  // every ID < 2^b - 1: sentinel sorts last
+
+  // keys: the packed edges, then scratch of the dedupe, then the part's local keys;
+  // ukeys: the distinct edges, then scratch of the local keys' sort.  Both go in the layout's plan.
+  DevBuf keys, ukeys, is_key;
+  PR_TRY(pack_inputs(g, E, src, dst, b, &keys, &is_key));
+  int64_t m = 0;
+  PR_TRY(sort_dedupe(g, E, b, &keys, &ukeys, &m));
+  Canon canon;
+  PR_TRY(canonical_csr(g, ukeys.as<uint64_t>(), m, b, is_key, &canon));
+  is_key.reset();
+  Order order;
+  PR_TRY(order_and_geometry(g, b, canon, &order));
+
+  // exchange lists (P > 1): which of this part's contributions every peer reads; cmap: global ->
+  // compacted gather position (P > 1, sparse exchange)
+  DevBuf cmap, orig;
+  PR_TRY(build_exchange(g, ukeys.as<uint64_t>(), m, b, (uint64_t(1) << b) - 1, order.rank_of.as<int32_t>(),
+                        order.gpos.as<int32_t>(), &cmap));
+  const int bg = bits_for((uint64_t)g->nparts * g->S_pad), brow = bits_for((uint64_t)g->n_rows);
+  PR_TRY(local_keys(g, m, b, bg, brow, canon, order, cmap, &ukeys, &keys, &orig));
+  order = Order{};
+
+  // work plans (fused: host greedy over the row pointers; split: pr_plan.hip on the GPU)
+  PR_TRY(g->C == 1 ? plan_fused(g, bg, brow, &keys, &ukeys, orig) : plan_split(g, bg, brow, cmap, &keys, &ukeys, orig));
+  PR_TRY(iteration_state(g));
+  keep_canonical(g, &canon);
+  PR_HIP(hipStreamSynchronize(g->stream));
   g->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
   return PR_OK;
 }

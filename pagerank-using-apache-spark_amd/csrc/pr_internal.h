@@ -9,16 +9,13 @@
 #include <vector>
 
 #include "pagerank_hip.h"
+#include "pr_layout.h"
 #include "pr_pieces.h"
 
 namespace pr {
 
 // ---- error plumbing ---------------------------------------------------------------------
 void set_error(const std::string &msg);
-struct Status {
-  int code = PR_OK;
-  bool ok() const { return code == PR_OK; }
-};
 int fail(int code, const std::string &msg);
 
 #define PR_HIP(call)                                                                          \
@@ -73,10 +70,6 @@ inline unsigned grid_for(int64_t n, int threads, unsigned cap = 1u << 20) {
   return (unsigned)g;
 }
 
-// ---- layouts (pr_graph.h) -----------------------------------------------------------------------
-constexpr int kLayoutFused = 0;  // one class, k_spmv_units (gather space <= 4 MiB)
-constexpr int kLayoutSplit = 1;  // column classes, LDS hot sets, partial slots (k_spmv_hot + k_epilogue_grp)
-
 // ---- SpMV work plan ------------------------------------------------------------------------
 // A unit is one workgroup of the SpMV launch.  STREAM: whole rows [r0, r0+meta) whose in-links
 // total n <= kUnitNnz.  PIECE: n <= kUnitNnz in-links of one long row r0; meta = -(piece+1).
@@ -97,16 +90,10 @@ __host__ __device__ inline int unit_n(const Unit &u) { return u.n & 0xFFFF; }
 __host__ __device__ inline int unit_cls(const Unit &u) { return u.n >> 16; }
 
 // ---- column classes (pr_graph.h "split" layout) -----------------------------------------------
-constexpr int kXcds = 8;                             // XCDs of the MI355X (one L2 each)
-constexpr int64_t kL2BytesPerXcd = 4ll << 20;        // class count: a class region should fit one L2
-constexpr int kMaxClasses = 128;                     // 8, 16, 32, 64 or 128 (PR_BOPT_CLASSES)
-constexpr int kAutoMaxClasses = 64;                  // the most the size policy picks by itself
+// kXcds, kMaxClasses and the layout policy: pr_layout.h
 // per-row class mask (rmask): ceil(C / 32) 32-bit words per row, class x in bit x % 32 of word
 // x / 32 (at 64 classes the two words are one little-endian u64)
 template <int C> constexpr int mask_words() { return (C + 31) / 32; }
-// split once the gather space passes 4 MiB: R-MAT s20 (5.2 MB, L2-resident either way) runs the
-// split layout at 8 classes in 0.09 ms/iter against 0.18 ms fused (profiles/r01/configs_ab/s20_*)
-constexpr int64_t kSplitMinSliceBytes = 4ll << 20;
 // Grouped epilogue (k_epilogue_grp): a wave takes kEpiGroup consecutive 64-row blocks and stages
 // their partial sums in an LDS window of kEpiWin slots, class runs a few at a time.
 constexpr int kEpiGroup = 8;
@@ -143,7 +130,6 @@ constexpr uint32_t kRowHole = 1u << 30;    // padding row of the class layout
 // derives each lane's scan metadata from the end marks (pr_spmv.h derive_meta).
 constexpr int kWavePT = 8;
 constexpr int kWaveUnit = 64 * kWavePT;  // 512 (wave64)
-constexpr int kHotThreads = 1024;        // 16 waves per CU: one workgroup per CU
 constexpr uint32_t kEntGlobal = 1u << 31;
 constexpr uint32_t kEntZero = 0u;  // LDS slot 0
 // Compact entry codes (one part, P = 1; round 3): the codes above cost 4 B per in-link, the
@@ -168,24 +154,9 @@ constexpr uint32_t kEntZero = 0u;  // LDS slot 0
 // kPieceAlign.  Gather position = k + tbl[x][k / kPieceAlign]: a per-class table of kPieceTbl
 // deltas (plus a 0 sentinel that keeps hot entries' loads out of range), restaged into LDS with
 // the hot set.  The hot set gives up kPieceTblSlots slots for it.
-constexpr int kCodeU32 = 0;
-constexpr int kCodeC20 = 1;
-constexpr int kCodeC24 = 2;
-constexpr int kCodeC20P = 3;
-constexpr int kCodeC24P = 4;
-// kC20IdxBits, kC24IdxBits and the piece-table constants: pr_pieces.h
-constexpr __host__ __device__ bool code_is_piece(int code) { return code >= kCodeC20P; }
-// LDS of k_spmv_hot: the hot set (slot 0 = 0.0, then the hot contributions of every part), one
-// more 0.0 slot (where compact cold entries point their LDS read), the workgroup's unit counter,
-// then one staging window of kStageSlots segment sums per wave (16 KiB in all; 128 beat 256 by
-// ~0.5 % and 64 by ~0.8 % at R-MAT s26, profiles/r01/stage_ab/).
-#ifndef PR_STAGE_SLOTS  // A/B builds only (tools/ab_build.sh): the library reads no environment
-#define PR_STAGE_SLOTS 128
-#endif
-constexpr int kStageSlots = PR_STAGE_SLOTS;
-constexpr int kHotLdsBytes = 160 * 1024;
-constexpr int kHotSlotsMax = (kHotLdsBytes - (kHotThreads / 64) * kStageSlots * 8) / 8 - 3;
-constexpr int kHotSlotsDefault = kHotSlotsMax;  // 18429 hot contributions (144 KiB)
+// The kCode* constants, which code a part takes, HotGeom and the LDS map of k_spmv_hot
+// (kHotThreads, kStageSlots, kHotLdsBytes, kHotSlots*): pr_layout.h; kC20IdxBits, kC24IdxBits and
+// the piece-table constants: pr_pieces.h
 
 // Geometry of the split layout of one part, passed to kernels by value.
 struct ClassGeom {
@@ -203,7 +174,6 @@ struct SlotPos {
 // Fused pack (pr_graph.h x_fused): where the epilogue stores the contributions the peers read (the
 // send runs of the buffer it writes, peer q's run at soff[q]; P = 0: no fused pack), and where
 // k_finalize stores the two slots that close every peer's run.
-constexpr int kMaxPackParts = 8;
 struct PackDst {
   double *sbuf;
   int P, self;
@@ -214,39 +184,5 @@ struct PackSlots {
   int n;
   int64_t off[kMaxPackParts];
 };
-
-// A class's hot set: for every part p, rows [x*Q_pad, + q_load) of p's slice go to LDS slots
-// 1 + [p*Kp, p*Kp + q_load); slot 0 holds 0.0.  Their gather positions come from a table (the
-// part's gather space is compacted when only some remote positions are received).
-struct HotGeom {
-  int C, P, Kp, q_load;
-  int64_t S_pad, Q_pad;
-  int tbl;  // 1: piece codes, the class's piece table follows the staging windows (kPieceTblSlots)
-  __host__ __device__ int slots() const { return P * Kp + 1; }
-  // slot `slots()` holds 0.0 (compact codes' cold entries read it), slot `slots() + 1` is a
-  // control word (the workgroup's unit counter, pr_spmv.h hot_class_units); the staging windows
-  // start 16-byte aligned after it
-  __host__ __device__ int ctr_slot() const { return slots() + 1; }
-  __host__ __device__ int stage_off() const { return (slots() + 3) & ~1; }
-  __host__ __device__ int tbl_off() const { return stage_off() + (kHotThreads / 64) * kStageSlots; }
-  __host__ __device__ size_t lds_bytes() const {
-    return sizeof(double) * ((size_t)tbl_off() + (tbl ? (size_t)kPieceTblSlots : 0));
-  }
-};
-
-// Host plan over a part's row_ptr: units, their source offsets in the unpadded column array,
-// long rows (split into pieces) and the padded column length.
-struct UnitPlan {
-  std::vector<Unit> units;
-  std::vector<int64_t> src_off;  // per unit: first in-link in the unpadded CSR
-  std::vector<int32_t> lr_row, lr_p0;
-  int64_t n_pieces = 0;
-  int64_t padded_len = 0;
-};
-// Plans rows [row_begin, row_end) (default: all rows); appends to *plan when append is true.
-void plan_units(const std::vector<int64_t> &rp, int unit_nnz, int unit_rows, UnitPlan *plan,
-                int64_t row_begin = 0, int64_t row_end = -1, bool append = false);
-// colp[8*p8 + i] = col[src_off + i] for every unit (padding entries are 0).
-int build_padded_cols(const UnitPlan &plan, const int32_t *col, int32_t *colp, hipStream_t s);
 
 }  // namespace pr

@@ -1,6 +1,7 @@
 // Piece codes of a row partition's parts (pr_internal.h kCodeC20P / kCodeC24P): the address
 // arithmetic shared by the build (pr_build.hip plan_pieces, k_fill_piece), the hot kernel
 // (pr_spmv.h cold_offset) and the CPU test shim (host/pieces_shim.cpp, tests/test_piece_codes_cpu.py).
+// Which parts take these codes, and how far the hot set shrinks for the table: pr_layout.h.
 // Plain C++ with PR_HD qualifiers, so a host compiler builds it without the HIP runtime.
 //
 // A part's class-x sources are its own class region plus, per peer, the sub-run of that peer's

@@ -1,9 +1,10 @@
 """A plain numpy model of the canonical graph build, an edge-list builder that lands on exact counts,
 and the launch arithmetic of the build's sort and compaction (TEST INFRASTRUCTURE ONLY).
 
-The device build (csrc/pr_build.hip) packs every record into a (dst << b | src) key, radix-sorts the
-keys (csrc/pr_sort.hip), drops adjacent duplicates with a two-launch compaction (csrc/pr_compact.h)
-and derives the in-link CSR, the out-degrees, the vertex flags and five counters.  `build` below
+The device build (csrc/pr_build.hip) packs every record into a (dst << b | src) key (its stage
+pack_inputs), radix-sorts the keys (csrc/pr_sort.hip) and drops adjacent duplicates with a
+two-launch compaction (csrc/pr_compact.h; sort_dedupe), and derives the in-link CSR, the
+out-degrees, the vertex flags and five counters (canonical_csr).  `build` below
 restates the result with np.unique and np.bincount; it shares no code with the library or with
 oracle/pagerank_oracle.c, and tests/test_build_model_cpu.py holds it to that oracle bit for bit.
 

@@ -1,5 +1,6 @@
-"""A plain model of the row partition (csrc/pr_build.hip, csrc/pr_exchange.hip): who owns a vertex,
-what every pair of parts exchanges, and the geometry that decides which code a part takes.  numpy
+"""A plain model of the row partition (csrc/pr_build.hip order_and_geometry and local_keys, csrc/
+pr_exchange.hip): who owns a vertex, what every pair of parts exchanges, and the geometry that
+decides which code a part takes (csrc/pr_layout.h, tests/test_layout_policy_cpu.py).  numpy
 only; it imports nothing from sparky_hip and loads no shared library.  tests/
 test_partition_model_cpu.py checks the model and the inputs below without a GPU, tests/
 test_gpu_partition_edges.py holds the library to the model.

@@ -1,6 +1,7 @@
 """CPU check of the piece-code address arithmetic (pr_internal.h kCodeC20P / kCodeC24P).
 
-The build (pr_build.hip plan_pieces / k_fill_piece) lays every class's pieces -- the own region and
+The build (pr_build.hip plan_split: choose_codes -> plan_pieces, fill_codes -> k_fill_piece; which
+parts take piece codes is pr_layout.h, tests/test_layout_policy_cpu.py) lays every class's pieces -- the own region and
 one sub-run of each peer's received run -- out in part order at kPieceAlign-aligned starts of a
 virtual index space and writes, per class, a table of byte deltas per 4096-entry block plus a 0
 sentinel; k_spmv_hot (pr_spmv.h cold_offset) turns an entry's index back into a byte offset with

@@ -478,6 +478,47 @@ int pr_batch_set_exclude(pr_batch *b, int32_t column, int32_t n, const int32_t *
  * ranks_out with k > 0: PR_ERR_INVALID; before pr_batch_reset: PR_ERR_STATE; k == 0: PR_OK and
  * every n_out[j] == 0.  Waits for the enqueued steps. */
 int pr_batch_get_topk_all(pr_batch *b, int32_t k, int32_t *ids_out, double *ranks_out, int32_t *n_out);
+/* Batch mixes: top-K lists of weighted blends of the batch's columns, with no iteration.  The
+ * iteration is linear in the teleport vector, so `width` computed columns (topics, single seeds, the
+ * plain run) answer any number of weighted combinations of them; negative weights list what is
+ * distinctive for a column (r_j - lambda * r_plain).
+ * The blend.  Mix i scores every vertex by m_i[v], formed over the columns j = 0 .. width-1 in
+ * ascending order under the weights w = weights[i*width .. (i+1)*width): a column whose weight is
+ * exactly 0.0 (either sign) takes no part; the first participating column gives acc = w_j * r_j[v],
+ * each later one acc = acc + w_j * r_j[v]; every product and every sum is rounded on its own (no
+ * fused multiply-add); a mix with no non-zero weight scores every vertex +0.0.  So a one-hot mix
+ * with weight 1.0 on column j is column j bit for bit, and a column driven to inf or NaN does not
+ * touch a mix that gives it weight 0.  r_j is what pr_batch_get_ranks(b, j, ...) returns at that
+ * moment; the mix does not care how the columns were produced (pr_batch_step, pr_batch_step_until,
+ * pr_batch_run_queue, either dangling mode).  Reading a mix whose weights sum to 1 as "the PageRank
+ * of the blended seeds" holds in PR_BATCH_DANGLING_UNIFORM (and under PR_DANGLING_NONE), for columns
+ * run the same number of iterations from the same init_ranks or to their fixed points; it does not
+ * hold in PR_BATCH_DANGLING_TELEPORT, whose dangling term is not linear in the teleport vector.
+ * pr_batch_mix_topk: mix i's list is ids_out / scores_out[i*k .. i*k + n_out[i]) with n_out[i] =
+ * min(k, V - n_exclude[i]); order, ties and the ordering of the IEEE bits are pr_get_topk's (score
+ * descending, ties by original ID ascending, exact inside tie classes); the scores are the bits
+ * pr_batch_mix_get returns for the same weights.  exclude[i][0 .. n_exclude[i]) are the vertices left
+ * out of mix i's list (n_exclude and exclude both NULL: none); a mix's set is its own: the columns'
+ * sets from pr_batch_set_exclude play no part, and those sets and every existing call are
+ * unaffected.  Waits for the enqueued steps; only the selected pairs cross to the host.
+ * pr_batch_mix_get: the dense blend of one mix (weights: width entries), V doubles in original-ID
+ * order.
+ * Errors.  A NULL batch, weights or n_out (scores_out for pr_batch_mix_get), n_mixes outside
+ * [1, PR_BATCH_MAX_MIXES], a non-finite weight, k < 0, NULL ids_out / scores_out with k > 0, exactly
+ * one of n_exclude / exclude NULL, n_exclude[i] < 0, NULL exclude[i] with n_exclude[i] > 0, an ID
+ * outside [0, V), a duplicate ID within one set: PR_ERR_INVALID, all checked on the host before any
+ * device call, nothing changed.  Before pr_batch_reset, or inside pr_batch_run_queue's callback:
+ * PR_ERR_STATE.  k == 0: PR_OK and every n_out[i] == 0.
+ * Memory.  The blends are materialised as a second interleaved matrix of V x stride_m doubles,
+ * stride_m = the next power of two >= the largest n_mixes seen; a uint16_t per vertex (bit i = "left
+ * out of mix i") once a mix has an exclusion set; the select over the blends has a scratch of its
+ * own.  All of it is allocated on first use, counted in pr_batch_info's device bytes from then on
+ * and freed with the batch; a batch that never mixes allocates nothing and launches nothing new. */
+#define PR_BATCH_MAX_MIXES 16
+int pr_batch_mix_topk(pr_batch *b, int32_t n_mixes, const double *weights /* n_mixes x width, row-major */,
+                      const int32_t *n_exclude, const int32_t *const *exclude /* per mix; both NULL: none */,
+                      int32_t k, int32_t *ids_out, double *scores_out, int32_t *n_out /* n_mixes */);
+int pr_batch_mix_get(pr_batch *b, const double *weights /* width */, double *scores_out /* V */);
 /* info[i] for i < min(n_info, 7): width, stride, work units, rows split over several units,
  * device bytes held by the batch, iterations done since the last reset, HIP-event time in ns of
  * the iterations of the last pr_batch_step call (-1: none yet, or they are still running). */

@@ -94,6 +94,9 @@ struct pr_batch {
   std::vector<uint16_t> h_mask;
   int64_t n_excl[pr::kBatchMaxWidth] = {0};
   pr::BTopkState *btopk = nullptr;  // scratch of pr_batch_get_topk_all
+  // pr_batch_mix_topk / pr_batch_mix_get (pr_batch_mix.hip): the blend matrix, the per-mix exclusion
+  // mask and a select scratch of their own, from the first mix call on
+  pr::BatchMixState *mix = nullptr;
   // pr_batch_step_until_any / pr_batch_run_queue: the device's BatchQueueState; a query's seed IDs
   // and values on their way into T (grown on demand); the queue's init_ranks (V doubles, on first
   // need: colbuf is taken by the queries of the done callback)
@@ -119,7 +122,7 @@ struct pr_batch {
     return units.bytes + long_row.bytes + long_p0.bytes + chunk_part.bytes + R.bytes + T.bytes + C[0].bytes +
            C[1].bytes + dc[0].bytes + dc[1].bytes + l1.bytes + part.bytes + colbuf.bytes + pr::topk_state_bytes(topk) +
            until.bytes + dcu.bytes + excl_mask.bytes + excl_oid.bytes + pr::btopk_state_bytes(btopk) + qstate.bytes +
-           qids.bytes + qvals.bytes + qinit.bytes + ts.bytes;
+           qids.bytes + qvals.bytes + qinit.bytes + ts.bytes + pr::batch_mix_bytes(mix);
   }
 };
 
@@ -811,6 +814,26 @@ int topk_all(pr_batch *b, int32_t k, int64_t narrow_div, int32_t *ids_out, doubl
                       b->n_excl, k, narrow_div, ids_out, ranks_out, n_out, info);
 }
 
+// pr_batch_mix_topk and its internal form: every PR_ERR_INVALID case on the host first, then the
+// state, then the blend and the select over it (pr_batch_mix.hip).
+int mix_topk(pr_batch *b, int32_t n_mixes, const double *weights, const int32_t *n_exclude,
+             const int32_t *const *exclude, int32_t k, int64_t narrow_div, int64_t grid_cap, int32_t *ids_out,
+             double *scores_out, int32_t *n_out, int64_t *info) {
+  if (!b) return fail(PR_ERR_INVALID, "NULL batch");
+  if (narrow_div < 0 || grid_cap < 0) return fail(PR_ERR_INVALID, "narrow_div < 0 or grid_cap < 0");
+  PR_TRY(batch_mix_check_topk(b->V, b->width, n_mixes, weights, n_exclude, exclude, k, ids_out, scores_out, n_out));
+  if (b->in_done_cb) return fail(PR_ERR_STATE, kInDoneCb);
+  if (!b->ready) return fail(PR_ERR_STATE, "pr_batch_mix_topk before pr_batch_reset");
+  if (info) info[0] = info[1] = 0, info[2] = info[3] = -1;
+  if (k == 0) {
+    std::fill(n_out, n_out + n_mixes, 0);
+    return PR_OK;
+  }
+  BatchDeviceGuard dg(b->device);
+  return batch_mix_topk(&b->mix, b->device, b->stream, b->R.as<double>(), b->V, b->width, b->stride, n_mixes, weights,
+                        n_exclude, exclude, k, narrow_div, grid_cap, ids_out, scores_out, n_out, info);
+}
+
 bool bad_tol(double tol) { return !(tol >= 0.0) || std::isinf(tol); }
 
 // The loop of pr_batch_step_until and (any) pr_batch_step_until_any: starts the device's state from
@@ -1381,6 +1404,34 @@ int pr_batch_topk_all_kernel_ns(const pr_batch *b, int64_t *ns_out) {
   return PR_OK;
 }
 
+int pr_batch_mix_topk(pr_batch *b, int32_t n_mixes, const double *weights, const int32_t *n_exclude,
+                      const int32_t *const *exclude, int32_t k, int32_t *ids_out, double *scores_out, int32_t *n_out) {
+  return pr::mix_topk(b, n_mixes, weights, n_exclude, exclude, k, pr::kTopkNarrowDiv, 0, ids_out, scores_out, n_out,
+                      nullptr);
+}
+
+// Internal entry point (not part of include/pagerank_hip.h): pr_batch_mix_topk with the select's
+// narrowing divisor (0: never narrow) and a cap on k_batch_mix's grid in workgroups (0: none), so that
+// tests reach the narrowed path and the later trips of the kernel's grid-stride loop at small sizes.
+// info[4] (may be NULL) = {histogram passes over the blend matrix, passes over the compacted
+// candidates, HIP-event time in ns of k_batch_mix, summed HIP-event time in ns of the select's
+// kernels}; the times are -1 where nothing ran.
+int pr_batch_mix_topk_ex(pr_batch *b, int32_t n_mixes, const double *weights, const int32_t *n_exclude,
+                         const int32_t *const *exclude, int32_t k, int32_t *ids_out, double *scores_out,
+                         int32_t *n_out, int64_t narrow_div, int64_t grid_cap, int64_t *info) {
+  return pr::mix_topk(b, n_mixes, weights, n_exclude, exclude, k, narrow_div, grid_cap, ids_out, scores_out, n_out, info);
+}
+
+int pr_batch_mix_get(pr_batch *b, const double *weights, double *scores_out) {
+  if (!b) return fail(PR_ERR_INVALID, "NULL batch");
+  PR_TRY(pr::batch_mix_check_get(b->width, weights, scores_out));
+  if (b->in_done_cb) return fail(PR_ERR_STATE, pr::kInDoneCb);
+  if (!b->ready) return fail(PR_ERR_STATE, "pr_batch_mix_get before pr_batch_reset");
+  pr::BatchDeviceGuard dg(b->device);
+  return pr::batch_mix_get(&b->mix, b->device, b->stream, b->R.as<double>(), b->V, b->width, b->stride, weights,
+                           b->colbuf.as<double>(), scores_out);
+}
+
 int pr_batch_info(const pr_batch *b, int64_t *info, int32_t n_info) {
   if (!b || !info) return fail(PR_ERR_INVALID, "NULL argument");
   if (b->in_done_cb) return fail(PR_ERR_STATE, pr::kInDoneCb);
@@ -1403,6 +1454,8 @@ void pr_batch_destroy(pr_batch *b) {
   b->topk = nullptr;
   pr::btopk_state_free(b->btopk);
   b->btopk = nullptr;
+  pr::batch_mix_free(b->mix);
+  b->mix = nullptr;
   if (b->ev0) (void)hipEventDestroy(b->ev0);
   if (b->ev1) (void)hipEventDestroy(b->ev1);
   hipStream_t s = b->stream;

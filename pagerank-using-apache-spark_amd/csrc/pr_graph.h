@@ -303,4 +303,26 @@ int btopk_select(BTopkState **state, int device, hipStream_t s, const double *R,
 int64_t btopk_kernel_ns(const BTopkState *t);
 size_t btopk_state_bytes(const BTopkState *t);
 void btopk_state_free(BTopkState *t);
+// Batch mixes (pr_batch_mix.hip): n_mixes weighted blends (weights: n_mixes x width, row-major) of
+// the columns of the interleaved V x stride rank matrix R, written to a V x stride_m matrix that
+// *state owns (created and grown on first need; the caller accounts for batch_mix_bytes and frees it
+// with batch_mix_free).  The two check functions are everything that can be PR_ERR_INVALID, on the
+// host alone.  batch_mix_topk then runs btopk_select over the blends with a mask built from the
+// per-mix sets (bit i: left out of mix i); grid_cap > 0 caps k_batch_mix's grid; info (may be NULL):
+// {histogram passes over the blends, those over the compacted candidates, HIP-event ns of
+// k_batch_mix, summed HIP-event ns of the select's kernels or -1}.  batch_mix_get blends one mix
+// and copies it to the host through colbuf (V doubles on the device).  Both wait for s.
+struct BatchMixState;
+int batch_mix_check_topk(int64_t V, int width, int32_t n_mixes, const double *weights, const int32_t *n_exclude,
+                         const int32_t *const *exclude, int32_t k, const int32_t *ids_out, const double *scores_out,
+                         const int32_t *n_out);
+int batch_mix_check_get(int width, const double *weights, const double *scores_out);
+int batch_mix_topk(BatchMixState **state, int device, hipStream_t s, const double *R, int64_t V, int width, int stride,
+                   int32_t n_mixes, const double *weights, const int32_t *n_exclude, const int32_t *const *exclude,
+                   int32_t k, int64_t narrow_div, int64_t grid_cap, int32_t *ids_out, double *scores_out, int32_t *n_out,
+                   int64_t *info);
+int batch_mix_get(BatchMixState **state, int device, hipStream_t s, const double *R, int64_t V, int width, int stride,
+                  const double *weights, double *colbuf, double *scores_out);
+size_t batch_mix_bytes(const BatchMixState *t);
+void batch_mix_free(BatchMixState *t);
 }  // namespace pr

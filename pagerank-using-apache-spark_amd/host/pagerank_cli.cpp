@@ -4,6 +4,7 @@
 //            [--save-every-iter] [--dangling=local|none] [--device N] [--quiet] [--stats]
 //            [--resume DIR/PageRank<i>] [--devices D0,D1,...] [--top K] [--seeds FILE]
 //            [--seed-set FILE]... [--exclude-seeds] [--tol X] [--seed-queue LISTFILE [--slots W]]
+//            [--dangling-to-seeds] [--mix W0,W1,...]...
 //
 // Input (libpagerank_host): "src dst" edge list ("src" alone = record without links), or
 // --format=ccjson "url<TAB>json" Common Crawl metadata records (Sparky.java:61-123).  URLs are
@@ -67,6 +68,14 @@
 // run's, not a set's; --seeds (the engine's own iteration) keeps the uniform term.  Output format
 // unchanged.
 //   pagerank edges.txt 20 --seed-set alice.txt --seed-set bob.txt --top 100 --dangling-to-seeds
+// --mix W0,W1,... (1 to 16 times; needs --seed-set and --top, not with --seed-queue; exactly one finite
+// number per --seed-set file; anything else is a usage error before any GPU work): after the per-set
+// listings, mix i prints "# mix <i>: <the weights as given>" and the --top listing of the blend
+// sum_j W_j * ranks_j of the sets' rankings, all mixes from one pr_batch_mix_topk call and no further
+// iteration.  Negative weights are allowed (1,-0.25: what set 0 ranks highly and set 1 does not).  With
+// --exclude-seeds a mix leaves out the seeds of every set it gives a non-zero weight.  The per-set
+// output is that of the run without --mix.
+//   pagerank edges.txt 20 --seed-set alice.txt --seed-set bob.txt --top 100 --mix 0.5,0.5 --mix 1,-0.25
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -96,6 +105,8 @@ struct Options {
   std::vector<std::string> seed_sets;  // --seed-set, in command-line order (empty: no batch)
   std::string seed_queue;              // --seed-queue LISTFILE (empty: no queue)
   int slots = 0;                       // --slots W (0: min(16, queries))
+  std::vector<std::string> mixes;      // --mix, as given, in command-line order
+  std::vector<double> mix_weights;     // mixes.size() x seed_sets.size(), row-major
 };
 
 std::vector<int> parse_devices(const std::string &s) {
@@ -129,8 +140,29 @@ std::vector<int> parse_devices(const std::string &s) {
                "                not with --seeds, --seed-set, --devices, --resume or --save-every-iter)\n"
                "                [--dangling-to-seeds]  (with --seed-set or --seed-queue: a set's dangling mass returns to\n"
                "                its own seeds instead of all URLs; a set whose teleport terms sum to 0 or overflow keeps the\n"
-               "                uniform term; the whole run's mode, not a set's; --seeds keeps the uniform term)\n");
+               "                uniform term; the whole run's mode, not a set's; --seeds keeps the uniform term)\n"
+               "                [--mix W0,W1,...]...  (with --seed-set and --top, 1 to 16 times: also list the K best\n"
+               "                URLs of the weighted blend of the sets' rankings, one finite weight per --seed-set;\n"
+               "                not with --seed-queue)\n");
   std::exit(2);
+}
+
+// --mix: n comma-separated finite numbers in plain decimal or exponent form, appended to *out.
+bool parse_mix(const std::string &text, size_t n, std::vector<double> *out) {
+  size_t i = 0, count = 0;
+  while (i <= text.size()) {
+    const size_t j = text.find(',', i);
+    const std::string t = text.substr(i, j == std::string::npos ? std::string::npos : j - i);
+    if (t.empty() || t.find_first_not_of("0123456789+-.eE") != std::string::npos) return false;
+    char *end = nullptr;
+    const double w = std::strtod(t.c_str(), &end);
+    if (*end != '\0' || !std::isfinite(w)) return false;
+    out->push_back(w);
+    ++count;
+    if (j == std::string::npos) break;
+    i = j + 1;
+  }
+  return count == n;
 }
 
 Options parse(int argc, char **argv) {
@@ -156,6 +188,9 @@ Options parse(int argc, char **argv) {
     else if (a.rfind("--seeds=", 0) == 0) o.seeds = a.substr(8);
     else if (a == "--seed-set" && i + 1 < argc) o.seed_sets.push_back(argv[++i]);
     else if (a.rfind("--seed-set=", 0) == 0) o.seed_sets.push_back(a.substr(11));
+    else if (a == "--mix" && i + 1 < argc) o.mixes.push_back(argv[++i]);
+    else if (a.rfind("--mix=", 0) == 0) o.mixes.push_back(a.substr(6));
+    else if (a == "--mix") usage("--mix takes one finite weight per --seed-set, separated by commas");
     else if (a == "--seed-queue" && i + 1 < argc) o.seed_queue = argv[++i];
     else if (a.rfind("--seed-queue=", 0) == 0) o.seed_queue = a.substr(13);
     else if ((a == "--slots" && i + 1 < argc) || a.rfind("--slots=", 0) == 0) {
@@ -192,6 +227,14 @@ Options parse(int argc, char **argv) {
   if (o.iterations < 0) usage("iterations must be >= 0");
   if (o.dangling_to_seeds && o.seed_sets.empty() && o.seed_queue.empty())
     usage("--dangling-to-seeds needs --seed-set or --seed-queue");
+  if (!o.mixes.empty()) {
+    if (!o.seed_queue.empty()) usage("--mix does not combine with --seed-queue");
+    if (o.seed_sets.empty() || o.top == 0) usage("--mix needs --seed-set and --top");
+    if (o.mixes.size() > 16) usage("--mix: at most 16 mixes");
+    for (const std::string &m : o.mixes)
+      if (!parse_mix(m, o.seed_sets.size(), &o.mix_weights))
+        usage("--mix takes one finite weight per --seed-set, separated by commas");
+  }
   if (!o.seed_queue.empty()) {
     if (!o.seeds.empty() || !o.seed_sets.empty() || !o.devices.empty() || !o.resume.empty() || o.save_every)
       usage("--seed-queue does not combine with --seeds, --seed-set, --devices, --resume or --save-every-iter");
@@ -355,6 +398,36 @@ int run_seed_sets(const Options &o, const prh_edges *edges, const std::vector<Se
       error = 1;
     }
     std::fflush(stdout);
+  }
+  if (rc == PR_OK && !o.mixes.empty() && !o.quiet) {  // the listings of all mixes from one call
+    const size_t n_mixes = o.mixes.size(), W = sets.size();
+    // --exclude-seeds: a mix leaves out the seeds of every set it gives a non-zero weight
+    std::vector<std::vector<int32_t>> excl(n_mixes);
+    std::vector<int32_t> n_excl(n_mixes, 0);
+    std::vector<const int32_t *> excl_ptr(n_mixes, nullptr);
+    for (size_t i = 0; i < n_mixes && o.exclude_seeds; ++i) {
+      for (size_t j = 0; j < W; ++j)
+        if (o.mix_weights[i * W + j] != 0.0) excl[i].insert(excl[i].end(), sets[j].ids, sets[j].ids + sets[j].n);
+      std::sort(excl[i].begin(), excl[i].end());
+      excl[i].erase(std::unique(excl[i].begin(), excl[i].end()), excl[i].end());
+      n_excl[i] = (int32_t)excl[i].size();
+      excl_ptr[i] = excl[i].empty() ? nullptr : excl[i].data();
+    }
+    std::vector<int32_t> mix_ids((size_t)top_k * n_mixes + 1), mix_n(n_mixes);
+    std::vector<double> mix_scores(mix_ids.size());
+    rc = pr_batch_mix_topk(b, (int32_t)n_mixes, o.mix_weights.data(), o.exclude_seeds ? n_excl.data() : nullptr,
+                           o.exclude_seeds ? excl_ptr.data() : nullptr, top_k, mix_ids.data(), mix_scores.data(),
+                           mix_n.data());
+    for (size_t i = 0; i < n_mixes && rc == PR_OK; ++i) {
+      std::printf("# mix %zu: %s\n", i, o.mixes[i].c_str());
+      std::fflush(stdout);
+      if (prh_write_has_rank_ids(edges, nullptr, mix_ids.data() + i * (size_t)top_k, mix_scores.data() + i * (size_t)top_k,
+                                 mix_n[i]) != 0) {
+        std::fprintf(stderr, "pagerank: %s\n", prh_last_error());
+        error = 1;
+      }
+      std::fflush(stdout);
+    }
   }
   const std::string err = rc == PR_OK ? std::string() : std::string(pr_last_error());
   pr_batch_destroy(b);  // before the graph it borrows

@@ -66,10 +66,12 @@ EXPORTED = [
     "pr_batch_destroy", "pr_batch_set_exclude", "pr_batch_get_topk_all", "pr_batch_step_until",
     "pr_batch_reset_column", "pr_batch_step_until_any", "pr_batch_run_queue",
     "pr_batch_set_dangling", "pr_batch_get_dangling", "pr_batch_get_teleport_sums",
+    "pr_batch_mix_topk", "pr_batch_mix_get",
 ]
 # pr_batch_info, in order
 BATCH_INFO_NAMES = ["width", "stride", "n_units", "n_long_rows", "device_bytes", "iters", "last_step_ns"]
 BATCH_MAX_WIDTH = 16
+BATCH_MAX_MIXES = 16  # PR_BATCH_MAX_MIXES
 # pr_batch_set_dangling's modes (PR_BATCH_DANGLING_*), by the name PageRankBatch.set_dangling takes
 PR_BATCH_DANGLING_UNIFORM = 0
 PR_BATCH_DANGLING_TELEPORT = 1
@@ -190,6 +192,11 @@ def load() -> ctypes.CDLL:
         "pr_batch_get_teleport_sums": ([P, P], ctypes.c_int),
         # internal: pr_batch_get_ranks for any column of the layout, [0, stride) -- the padding columns too
         "pr_batch_get_ranks_ex": ([P, i32, P], ctypes.c_int),
+        # b, n_mixes, weights, n_exclude, exclude (an array of pointers), k, ids_out, scores_out, n_out
+        "pr_batch_mix_topk": ([P, i32, P, P, P, i32, P, P, P], ctypes.c_int),
+        "pr_batch_mix_get": ([P, P, P], ctypes.c_int),
+        # internal: pr_batch_mix_topk with the select's narrowing divisor, a cap on the mix kernel's grid and info[4]
+        "pr_batch_mix_topk_ex": ([P, i32, P, P, P, i32, P, P, P, i64, i64, P], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         if name in OPTIONAL and not hasattr(L, name):

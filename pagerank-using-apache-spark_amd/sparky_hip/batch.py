@@ -12,6 +12,8 @@ on the device.  ``run_queue(queries, max_iterations, tol)`` serves any number of
 columns, refilling a column (``reset_column``) as soon as its query is done (``step_until_any``).
 ``set_dangling("teleport")`` returns every column's dangling mass along its own teleport vector
 instead of spreading it over all vertices; ``teleport_sums()`` reports the vectors' sums it divides by.
+``mix_topk(weights, k)`` returns the top-K lists of up to 16 weighted blends of the columns, formed and
+selected on the device with no further iteration; ``mix(weights)`` returns one dense blend.
 """
 from __future__ import annotations
 
@@ -252,6 +254,66 @@ class PageRankBatch:
             check(L.pr_batch_topk_all_kernel_ns(self._h, ctypes.byref(ns)))
             out["kernel_ns"] = ns.value
         return lists, out
+
+    # -- mixes -------------------------------------------------------------------------------
+    def _mix_weights(self, weights, one: bool) -> np.ndarray:
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.ndim == 1 and w.shape[0] == self.width:
+            w = w.reshape(1, self.width)
+        if w.ndim != 2 or w.shape[1] != self.width or (one and w.shape[0] != 1):
+            raise ValueError("weights must have shape (width,)" + ("" if one else " or (n_mixes, width)"))
+        return w
+
+    def mix(self, weights) -> np.ndarray:
+        """pr_batch_mix_get: float64[V], the blend sum_j weights[j] * ranks(j) as the device forms it
+        (columns ascending, a weight of exactly 0 skipped, every product and sum rounded on its own)."""
+        w = self._mix_weights(weights, True)
+        out = np.zeros(max(self.n_vertices, 1), np.float64)
+        check(_lib.load().pr_batch_mix_get(self._h, _ptr(w), _ptr(out)))
+        return out[: self.n_vertices]
+
+    def mix_topk(self, weights, k: int, exclude=None):
+        """pr_batch_mix_topk: the top-``k`` lists of up to 16 weighted blends of the columns, selected on
+        the device with no iteration.  ``weights``: (n_mixes, width) or (width,); ``exclude``: None, or
+        per mix a sequence of vertex IDs left out of that mix's list (None or empty: none).  Returns a
+        list of n_mixes pairs (ids int32[n_i], scores float64[n_i]) in ``topk``'s order; the scores are
+        the bits ``mix`` returns for the same weights."""
+        return self._mix_topk(weights, k, exclude, None)[0]
+
+    def _mix_topk_ex(self, weights, k: int, exclude=None, *, narrow_div: int = 8, grid_cap: int = 0):
+        """The library's internal entry point behind mix_topk(): the same query with the select's
+        narrowing divisor (0: never) and a cap on the mix kernel's grid in workgroups (0: none).
+        Returns (lists, info) with info = {matrix_passes, cand_passes, mix_ns, select_ns}.  For tests and
+        tools/batch_mix_bench.py."""
+        return self._mix_topk(weights, k, exclude, (int(narrow_div), int(grid_cap)))
+
+    def _mix_topk(self, weights, k: int, exclude, ex):
+        w = self._mix_weights(weights, False)
+        m, k = int(w.shape[0]), int(k)
+        n_ex, ptrs, keep = None, None, []
+        if exclude is not None:
+            if len(exclude) != m:
+                raise ValueError("exclude needs one entry per mix")
+            n_ex, ptrs = np.zeros(m, np.int32), (ctypes.c_void_p * m)()
+            for i, ids in enumerate(exclude):
+                x = np.zeros(0, np.int32) if ids is None else np.ascontiguousarray(ids, dtype=np.int32)
+                if x.ndim != 1:
+                    raise ValueError("an exclusion set must be a 1-D array")
+                keep.append(x)
+                n_ex[i] = x.shape[0]
+                ptrs[i] = x.ctypes.data if x.shape[0] else None
+        ids, sc = np.zeros(max(k, 1) * m, np.int32), np.zeros(max(k, 1) * m, np.float64)
+        n = np.zeros(m, np.int32)
+        info = np.zeros(4, np.int64)
+        L = _lib.load()
+        head = (self._h, m, _ptr(w), _ptr(n_ex) if n_ex is not None else None,
+                ctypes.cast(ptrs, ctypes.c_void_p) if ptrs is not None else None, k, _ptr(ids), _ptr(sc), _ptr(n))
+        if ex is None:
+            check(L.pr_batch_mix_topk(*head))
+        else:
+            check(L.pr_batch_mix_topk_ex(*head, ex[0], ex[1], _ptr(info)))
+        lists = [(ids[i * k: i * k + int(n[i])].copy(), sc[i * k: i * k + int(n[i])].copy()) for i in range(m)]
+        return lists, dict(zip(("matrix_passes", "cand_passes", "mix_ns", "select_ns"), (int(x) for x in info)))
 
     def info(self) -> dict:
         a = np.zeros(len(_lib.BATCH_INFO_NAMES), np.int64)

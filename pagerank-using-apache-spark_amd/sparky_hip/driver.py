@@ -3,7 +3,8 @@
 CLI: ``python -m sparky_hip <input-path> [iterations=10] [--format edges|ccjson]
 [--out DIR] [--save-every-iter] [--dangling=local|none] [--device N] [--quiet]
 [--resume DIR/PageRank<i>] [--devices D0,D1,...] [--top K] [--seeds FILE] [--seed-set FILE]...
-[--exclude-seeds] [--tol X] [--seed-queue LISTFILE [--slots W]] [--dangling-to-seeds]``
+[--exclude-seeds] [--tol X] [--seed-queue LISTFILE [--slots W]] [--dangling-to-seeds]
+[--mix W0,W1,...]...``
 
 * input: text edge list, ``src dst`` per line; a single-token line ``src`` is a record without
   ``a`` links (Sparky.java:114-118).  Tokens (URLs) are taken verbatim and interned to dense
@@ -62,6 +63,14 @@ CLI: ``python -m sparky_hip <input-path> [iterations=10] [--form
   ``--dangling=none`` there is no dangling mass and the option changes nothing.  The mode is the
   whole run's, not a set's; ``--seeds`` (the engine's own iteration) keeps the uniform term.  Output
   format unchanged, same bytes as the C++ CLI.
+* ``--mix W0,W1,...`` (1 to 16 times; needs ``--seed-set`` and ``--top``, not with ``--seed-queue``; exactly
+  one finite number per ``--seed-set`` file; anything else is a usage error before any GPU work): after
+  the per-set listings, mix i prints ``# mix <i>: <the weights as given>`` and the ``--top`` listing of
+  the blend ``sum_j W_j * ranks_j`` of the sets' rankings, all mixes from one
+  ``PageRankBatch.mix_topk`` call and no further iteration.  Negative weights are allowed (``1,-0.25``:
+  what set 0 ranks highly and set 1 does not).  With ``--exclude-seeds`` a mix leaves out the seeds of
+  every set it gives a non-zero weight.  The per-set output is that of the run without ``--mix``.  Same
+  bytes as the C++ CLI.
 """
 from __future__ import annotations
 
@@ -246,6 +255,18 @@ def _run_seed_sets(edges, a, sets, top, out) -> None:
                     edges.write_has_rank_ids(None, *tops[j])
                 else:
                     edges.write_has_rank(None, ranks)
+            if a.mix and not a.quiet:  # the listings of all mixes from one call (PageRankBatch.mix_topk)
+                weights = np.array(a.mix_weights, np.float64)
+                excl = None
+                if a.exclude_seeds:  # a mix leaves out the seeds of every set it gives a non-zero weight
+                    excl = [np.unique(np.concatenate([np.zeros(0, np.int32)] +
+                                                     [sets[j][0] for j in range(len(sets)) if w[j] != 0.0]))
+                            for w in weights]
+                lists = b.mix_topk(weights, min(top, edges.n_vertices), excl)
+                for i, given in enumerate(a.mix):
+                    out.write(f"# mix {i}: {given}\n")
+                    out.flush()
+                    edges.write_has_rank_ids(None, *lists[i])
 
 
 def read_seed_queue(path: str) -> List[str]:
@@ -285,8 +306,26 @@ def _run_seed_queue(edges, a, files, sets, top, out) -> None:
         edges.write_has_rank_ids(None, *rec["topk"])
 
 
+def parse_mix(text: str, n: int):
+    """--mix: ``n`` comma-separated finite numbers in plain decimal or exponent form; None if not."""
+    toks = text.split(",")
+    if len(toks) != n or any(not t or set(t) - set("0123456789+-.eE") for t in toks):
+        return None
+    try:
+        w = [float(t) for t in toks]
+    except ValueError:
+        return None
+    return w if all(math.isfinite(x) for x in w) else None
+
+
 def main(argv=None) -> int:
     from ._host import HostEdges, HostError, seed_teleport
+
+    # "--mix -1,0.5": the value starts with '-', which argparse would read as an option
+    argv = list(sys.argv[1:] if argv is None else argv)
+    for i in range(len(argv) - 1, 0, -1):
+        if argv[i - 1] == "--mix":
+            argv[i - 1: i + 1] = ["--mix=" + argv[i]]
 
     ap = argparse.ArgumentParser(prog="sparky_hip", description=__doc__.splitlines()[0])
     ap.add_argument("edge_list")
@@ -319,7 +358,20 @@ def main(argv=None) -> int:
                     help="with --seed-set or --seed-queue: a set's dangling mass returns to its own seeds instead of "
                          "all URLs; a set whose teleport terms sum to 0 or overflow keeps the uniform term; the whole run's "
                          "mode, not a set's; --seeds keeps the uniform term")
+    ap.add_argument("--mix", action="append", default=None, metavar="W0,W1,...",
+                    help="with --seed-set and --top, 1 to 16 times: also list the K best URLs of the weighted blend of "
+                         "the sets' rankings, one finite weight per --seed-set; not with --seed-queue")
     a = ap.parse_args(argv)
+    if a.mix:
+        if a.seed_queue is not None:
+            ap.error("--mix does not combine with --seed-queue")
+        if not a.seed_set or a.top is None:
+            ap.error("--mix needs --seed-set and --top")
+        if len(a.mix) > 16:
+            ap.error("--mix: at most 16 mixes")
+        a.mix_weights = [parse_mix(m, len(a.seed_set)) for m in a.mix]
+        if any(w is None for w in a.mix_weights):
+            ap.error("--mix takes one finite weight per --seed-set, separated by commas")
     if a.slots is not None:
         if not (a.slots.isdigit() and len(a.slots) <= 2 and 1 <= int(a.slots) <= 16):
             ap.error("--slots takes a count W in 1..16")

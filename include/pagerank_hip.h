@@ -182,8 +182,8 @@ int pr_get_ranks(pr_graph *g, double *ranks_out);
  * itself*, not a probability: a vector of all 0.15 gives ranks bitwise equal to the scalar run.
  * While a vector is set, the scalar `teleport` of pr_reset / pr_run / pr_group_reset is ignored;
  * `damping` still applies.  Everything else stays Sparky's: ranks are never normalised, S = r_old
- * for rows without in-links, and the dangling term stays the uniform dc / N -- redistributing the
- * dangling mass according to t is out of scope.
+ * for rows without in-links, and the dangling term is the uniform dc / N unless
+ * pr_set_teleport_dangling (below) returns the dangling mass along t.
  * The vector is a property of the handle: it survives pr_reset and pr_run (which reset ranks
  * only), takes effect from the next iteration enqueued after the call, and is cleared by passing
  * NULL (back to the scalar).  Both calls wait for the enqueued steps, like pr_get_ranks, and are
@@ -200,6 +200,38 @@ int pr_get_ranks(pr_graph *g, double *ranks_out);
 int pr_set_teleport(pr_graph *g, const double *teleport);
 /* t[ids[i]] = values[i], every other vertex `rest`.  ids must be distinct and in [0, V). */
 int pr_set_teleport_sparse(pr_graph *g, int32_t n, const int32_t *ids, const double *values, double rest);
+
+/* Where the dangling mass goes while a teleport vector is set.  PR_TELEPORT_DANGLING_UNIFORM (the
+ * default) is the iteration above, bit for bit.  PR_TELEPORT_DANGLING_TELEPORT returns it along the
+ * vector, as textbook personalised PageRank does and as PR_BATCH_DANGLING_TELEPORT does for a batch
+ * column: with ts = sum_v t[v],
+ *     q     = dc / ts                               (one rounded divide, per launch)
+ *     r'[v] = t[v] + damping * (S[v] + q * t[v])
+ * every operation rounded on its own (no contraction); S, dc, the in-degree-0 rule, c' = r' / d, the
+ * norms, the slots and the exchange are those of the uniform mode, and PR_STAT_LAST_DC and the
+ * callback's dangling_sum stay dc.  With t = (0.15 N) p for a probability vector p the term is
+ * dc * p[v]: the mass goes back to the seeds, and a vertex the seeds cannot reach drains towards 0.
+ * ts runs over all V original IDs, not over a part's rows.  Every part forms it on the host from the
+ * arguments of its own pr_set_teleport / pr_set_teleport_sparse call, in one fixed order: blocks of
+ * 1024 consecutive IDs (the last one shorter), each summed sequentially in ID order from +0.0, the
+ * block sums added sequentially in block order.  So ts depends on the vector and V only: it has the
+ * same bits on every part, in every layout, and for a sparse set and the equal dense vector, and the
+ * mode needs no communication beyond the exchange of the uniform mode.
+ * Fallback, decided on the host when an iteration is enqueued: with the mode off, without a vector,
+ * on a PR_DANGLING_NONE graph, or with a ts that is exactly 0 or not finite (a negative ts is
+ * allowed), the handle launches exactly the kernels it launches without the mode.
+ * The mode is a property of the handle, next to the vector: it survives pr_reset, pr_run, and
+ * clearing and re-setting the vector.  pr_set_teleport_dangling waits for the enqueued steps, like
+ * pr_set_teleport, is valid any time after create and takes effect from the next iteration
+ * enqueued; it allocates no device memory (PR_INFO_DEVICE_BYTES does not move).  Like the vector it
+ * is local, not collective: the parts of a group or of RCCL ranks are set alike.
+ * pr_get_teleport_sum gives ts of the vector in force (0.0 without one), in either mode.
+ * A NULL graph or output, or a mode other than the two constants: PR_ERR_INVALID, nothing changed. */
+#define PR_TELEPORT_DANGLING_UNIFORM 0
+#define PR_TELEPORT_DANGLING_TELEPORT 1
+int pr_set_teleport_dangling(pr_graph *g, int32_t mode);
+int pr_get_teleport_dangling(const pr_graph *g, int32_t *mode_out);
+int pr_get_teleport_sum(pr_graph *g, double *sum_out);
 
 /* Top-K query, selected on the device: the k highest-ranked vertices of this part (the rows it
  * owns; with one part, of the graph), rank descending, ties broken by original vertex ID
@@ -433,8 +465,9 @@ int pr_batch_run_queue(pr_batch *b, int32_t n_queries, const pr_batch_query *que
  * pr_batch_set_dangling waits for the enqueued steps, is valid any time after create, survives
  * pr_batch_reset and takes effect from the next iteration enqueued.  The width doubles of ts are
  * allocated with the first use of the mode or of the getter and counted in pr_batch_info's device
- * bytes from then on.  The mode is the batch's: there is no per-column or per-query mode, and the
- * engine's own iteration (pr_set_teleport, pr_step, pr_group_*) keeps the uniform term.
+ * bytes from then on.  The mode is the batch's: there is no per-column or per-query mode; the
+ * engine's own iteration (pr_set_teleport, pr_step, pr_group_*) has the same choice per handle,
+ * pr_set_teleport_dangling.
  * A NULL batch or output, a mode other than the two constants: PR_ERR_INVALID, nothing changed;
  * inside pr_batch_run_queue's callback: PR_ERR_STATE. */
 #define PR_BATCH_DANGLING_UNIFORM 0

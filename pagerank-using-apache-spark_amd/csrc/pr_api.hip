@@ -295,6 +295,26 @@ int pr_set_teleport_sparse(pr_graph *g, int32_t n, const int32_t *ids, const dou
   return pr::set_teleport_sparse(g, n, ids, values, rest);
 }
 
+int pr_set_teleport_dangling(pr_graph *g, int32_t mode) {
+  if (!g) return fail(PR_ERR_INVALID, "NULL graph");
+  if (mode != PR_TELEPORT_DANGLING_UNIFORM && mode != PR_TELEPORT_DANGLING_TELEPORT)
+    return fail(PR_ERR_INVALID, "mode: PR_TELEPORT_DANGLING_UNIFORM or PR_TELEPORT_DANGLING_TELEPORT");
+  DeviceGuard dg(g->device);
+  return pr::set_teleport_dangling(g, mode);
+}
+
+int pr_get_teleport_dangling(const pr_graph *g, int32_t *mode_out) {
+  if (!g || !mode_out) return fail(PR_ERR_INVALID, "NULL argument");
+  *mode_out = g->tele_dangling;
+  return PR_OK;
+}
+
+int pr_get_teleport_sum(pr_graph *g, double *sum_out) {
+  if (!g || !sum_out) return fail(PR_ERR_INVALID, "NULL argument");
+  *sum_out = g->tele_on ? g->tele_sum : 0.0;
+  return PR_OK;
+}
+
 int pr_step(pr_graph *g, int32_t iterations) {
   if (!g || iterations < 0) return fail(PR_ERR_INVALID, "bad argument");
   DeviceGuard dg(g->device);

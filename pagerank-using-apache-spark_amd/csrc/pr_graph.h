@@ -127,6 +127,11 @@ struct pr_graph {
   // destroy; while tele_on, the update kernels read tele[row] and ignore the scalar above.
   pr::DevBuf tele;
   bool tele_on = false;
+  // where the dangling mass goes while tele_on (pr_set_teleport_dangling; survives reset, run and
+  // clearing the vector), and ts = the sum of the whole vector over all V IDs in pr_tele_sum.h's
+  // order (formed on the host by every set; 0.0 without a vector)
+  int32_t tele_dangling = PR_TELEPORT_DANGLING_UNIFORM;
+  double tele_sum = 0.0;
   int cur = 0;  // cbuf[cur] holds the contributions of the current ranks
   int64_t iters_done = 0;
   bool ready = false;  // pr_reset was called
@@ -229,6 +234,8 @@ int prepare_tele_kernels(const pr_graph *g);  // the same for the epilogue that 
 int set_teleport_dense(pr_graph *g, const double *teleport);
 int set_teleport_sparse(pr_graph *g, int32_t n, const int32_t *ids, const double *values, double rest);
 int clear_teleport(pr_graph *g);
+int prepare_tele_dangling_kernels(const pr_graph *g);  // the kTeleDangling epilogue's dynamic LDS
+int set_teleport_dangling(pr_graph *g, int32_t mode);  // waits for g's enqueued work first
 // the heavy-row pass (k_spmv_hot) on g's stream, hot phases [ph0, ph1) (-1: all)
 int launch_hot(pr_graph *g, int in_buf, int ph0 = 0, int ph1 = -1);
 int join_exchange(pr_graph *g);  // g's stream waits for a pending overlapped exchange

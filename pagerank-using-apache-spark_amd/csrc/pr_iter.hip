@@ -22,19 +22,23 @@
 //                    cdna_hip_programming.md Guideline 16).
 //   P > 1: the exchange (pr_exchange.hip) sends every peer the contributions its in-links read.
 //   Personalised PageRank (pr_set_teleport): while a handle holds a teleport vector, the three
-//   update sites (k_spmv_units, k_finalize's long rows, k_epilogue_grp) run as their TELE
+//   update sites (k_spmv_units, k_finalize's long rows, k_epilogue_grp) run as their kTeleOn
 //   instantiations, which read the row's own term t[row] in place of the scalar 0.15; a handle
-//   without one launches the TELE = false instantiations, the kernels it always launched.
+//   without one launches the kTeleOff instantiations, the kernels it always launched.  With
+//   pr_set_teleport_dangling's mode on they run as the kTeleDangling instantiations, which return the
+//   dangling mass along t: q * t[row] with q = dc / ts in the launch-wide dc / N's place (tele_form).
 //
 // Every sum has a fixed order, so results are bitwise reproducible run to run.
 #include <algorithm>
 #include <climits>
 #include <vector>
 
+#include "pr_batch_dangling.h"
 #include "pr_device.h"
 #include "pr_graph.h"
 #include "pr_ipc_protocol.h"
 #include "pr_spmv.h"
+#include "pr_tele_sum.h"
 
 namespace pr {
 namespace {
@@ -48,7 +52,9 @@ __device__ __forceinline__ double load_sc1(const double *p) {
       reinterpret_cast<const unsigned long long *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 }
 
-template <bool TELE>
+// TM: the form of the long rows' update (pr_spmv.h kTeleOff / kTeleOn / kTeleDangling; with the last
+// the argument `n_vertices` carries ts)
+template <int TM>
 __global__ __launch_bounds__(kThreads) void k_finalize(
     int64_t n_long, const int32_t *__restrict__ lr_row, const int32_t *__restrict__ lr_p0,
     const double *__restrict__ piece_part, const double2 *__restrict__ parts, int64_t n_parts,
@@ -56,6 +62,7 @@ __global__ __launch_bounds__(kThreads) void k_finalize(
     double *__restrict__ cout, SlotPos sp, double n_vertices, double teleport,
     double damping, double *__restrict__ fin_part, unsigned *__restrict__ counter,
     double *__restrict__ slot_out, PackSlots ps, const double *__restrict__ tele) {
+  constexpr bool TELE = TM != kTeleOff;
   __shared__ double red[kThreads / kWave];
   __shared__ int is_last;
   const int t = threadIdx.x, lane = lane_id();
@@ -73,7 +80,7 @@ __global__ __launch_bounds__(kThreads) void k_finalize(
         const double rold = r[v];
         double tv = teleport;
         if constexpr (TELE) tv = tele[v];
-        const double rn = affine(acc, tdc, tv, damping);
+        const double rn = affine(acc, tele_dangling_term<TM>(tdc, tv), tv, damping);
         r[v] = rn;
         const uint32_t info = rowinfo[v];
         const uint32_t d = info & kRowDegMask;
@@ -141,6 +148,16 @@ __global__ __launch_bounds__(kThreads) void k_reset(int64_t n_rows, const double
   if (threadIdx.x == 0) parts[blockIdx.x] = make_double2(dcp, 0.0);
 }
 
+// The form of the update sites for the next launch, decided on the host: the kernels of a handle
+// without a vector (kTeleOff), with one (kTeleOn), or -- pr_set_teleport_dangling's mode on, a graph
+// that counts dangling mass, and a sum ts that is finite and not 0 -- the kTeleDangling kernels, which
+// return the dangling mass along the vector.  Every other case launches exactly what it always did.
+int tele_form(const pr_graph *g) {
+  if (!g->tele_on) return kTeleOff;
+  if (g->tele_dangling != PR_TELEPORT_DANGLING_TELEPORT || (g->flags & PR_DANGLING_NONE)) return kTeleOn;
+  return batch_dangling_uses_teleport(g->tele_sum) ? kTeleDangling : kTeleOn;
+}
+
 int launch_finalize(pr_graph *g, int64_t n_long, const double2 *parts, int64_t n_parts, int in_buf,
                     int out_buf, hipStream_t stream) {
   double *cout = g->cbuf[out_buf].as<double>() + g->own_off;
@@ -151,11 +168,13 @@ int launch_finalize(pr_graph *g, int64_t n_long, const double2 *parts, int64_t n
       if (q != g->part) ps.off[ps.n++] = g->x_soff[q + 1] - 2;
   }
   // the per-row teleport terms matter to the long rows only (the reset's call has none)
-  const bool tele = g->tele_on && n_long > 0;
-  hipLaunchKernelGGL((tele ? k_finalize<true> : k_finalize<false>), dim3(g->fin_blocks), dim3(kThreads), 0, stream,
+  const int tm = n_long > 0 ? tele_form(g) : kTeleOff;
+  const bool tele = tm != kTeleOff;
+  hipLaunchKernelGGL((tm == kTeleDangling ? k_finalize<kTeleDangling> : tele ? k_finalize<kTeleOn> : k_finalize<kTeleOff>),
+                     dim3(g->fin_blocks), dim3(kThreads), 0, stream,
                      n_long, g->lr_row.as<int32_t>(), g->lr_p0.as<int32_t>(), g->piece_part.as<double>(),
                      parts, n_parts, g->r.as<double>(), g->rowinfo.as<uint32_t>(),
-                     g->cbuf[in_buf].as<double>(), cout, g->slots, (double)g->V,
+                     g->cbuf[in_buf].as<double>(), cout, g->slots, tm == kTeleDangling ? g->tele_sum : (double)g->V,
                      g->teleport, g->damping, g->fin_part.as<double>(), g->fin_counter.as<unsigned>(),
                      cout + g->S_pad - 2, ps, tele ? g->tele.as<double>() : nullptr);
   PR_HIP(hipGetLastError());
@@ -193,12 +212,22 @@ int prepare_hot_kernel() {
   return PR_OK;
 }
 
-// The TELE instantiations of k_epilogue_grp get the same dynamic-LDS allowance, on the first
+// The kTeleOn instantiations of k_epilogue_grp get the same dynamic-LDS allowance, on the first
 // pr_set_teleport of a handle (current device): a handle that never sets a vector never asks.
 int prepare_tele_kernels(const pr_graph *g) {
   if (g->C <= 1) return PR_OK;
-  PR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(epi_grp_kernel(g->C, g->epi_walk, g->epi_narrow, true)),
+  PR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(epi_grp_kernel(g->C, g->epi_walk, g->epi_narrow, kTeleOn)),
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)epi_grp_lds(g->epi_narrow)));
+  return PR_OK;
+}
+
+// And the kTeleDangling instantiation, when pr_set_teleport_dangling turns the mode on (current
+// device): a handle that never asks for the mode never asks for this.
+int prepare_tele_dangling_kernels(const pr_graph *g) {
+  if (g->C <= 1) return PR_OK;
+  PR_HIP(hipFuncSetAttribute(
+      reinterpret_cast<const void *>(epi_grp_kernel(g->C, g->epi_walk, g->epi_narrow, kTeleDangling)),
+      hipFuncAttributeMaxDynamicSharedMemorySize, (int)epi_grp_lds(g->epi_narrow)));
   return PR_OK;
 }
 
@@ -459,14 +488,19 @@ int iter_compute(pr_graph *g) {
   PR_TRY(mark_start());
   // the handle's teleport vector (pr_set_teleport), or nullptr: the scalar
   const double *tele = g->tele_on ? g->tele.as<double>() : nullptr;
+  // the update's form, and what divides dc: N, or ts where the dangling mass follows the vector
+  const int tm = tele_form(g);
+  const double divisor = tm == kTeleDangling ? g->tele_sum : (double)g->V;
   // light rows (all rows when C == 1): fused single pass
   if (g->n_units > 0)
-    hipLaunchKernelGGL((tele ? k_spmv_units<kPerThread, true, true> : k_spmv_units<kPerThread, true, false>),
+    hipLaunchKernelGGL((tm == kTeleDangling ? k_spmv_units<kPerThread, true, kTeleDangling>
+                        : tm == kTeleOn     ? k_spmv_units<kPerThread, true, kTeleOn>
+                                            : k_spmv_units<kPerThread, true, kTeleOff>),
                        dim3((unsigned)g->n_units), dim3(kThreads), 0, s,
                        g->units.as<Unit>(), g->rowptr.as<int64_t>(), g->colp.as<int32_t>(),
                        g->cbuf[in].as<double>(), g->cbuf[out].as<double>() + own, g->r.as<double>(),
                        g->rowinfo.as<uint32_t>(), g->piece_part.as<double>(), g->unit_part.as<double2>(),
-                       g->slots, g->S_pad, (double)g->V, g->teleport, g->damping, tele);
+                       g->slots, g->S_pad, divisor, g->teleport, g->damping, tele);
   int64_t n_parts = g->n_units;
   if (g->C > 1) {  // split layout: class units, long segments, then the epilogue over all rows
     if (phased_wait) {
@@ -487,7 +521,7 @@ int iter_compute(pr_graph *g) {
       hipLaunchKernelGGL(k_seg_reduce, dim3(grid_for(g->n_segs, kThreads / kWave, 4096)), dim3(kThreads), 0, s,
                          g->n_segs, g->seg_slot.as<int64_t>(), g->seg_p0.as<int32_t>(), g->piece_part.as<double>(),
                          g->partial.as<double>());
-    const EpiGrpFn epi = epi_grp_kernel(g->C, g->epi_walk, g->epi_narrow, tele != nullptr);
+    const EpiGrpFn epi = epi_grp_kernel(g->C, g->epi_walk, g->epi_narrow, tm);
     PackDst pd{};  // fused pack: c' straight into the send runs paired with buffer `out`
     if (g->x_fused) {
       pd.sbuf = send_runs(g, out);
@@ -502,7 +536,7 @@ int iter_compute(pr_graph *g) {
       hipLaunchKernelGGL(epi, dim3(grid), dim3(epi_grp_threads(g->epi_narrow)), epi_grp_lds(g->epi_narrow), s,
                          g->nblk, g_lo, g_hi, g->partial.as<double>(), g->rmask.p, g->cbase.as<int32_t>(),
                          g->rowinfo.as<uint32_t>(), g->r.as<double>(), g->cbuf[out].as<double>() + own,
-                         g->cbuf[in].as<double>(), g->slots, (double)g->V, g->teleport, g->damping,
+                         g->cbuf[in].as<double>(), g->slots, divisor, g->teleport, g->damping,
                          g->unit_part.as<double2>() + g->n_units, g->eoff.as<int64_t>(), g->epos.as<uint16_t>(),
                          g->x_pmask.as<uint8_t>(), g->x_sbase.as<int32_t>(), ord, pd, tele);
       PR_HIP(hipGetLastError());
@@ -650,9 +684,17 @@ int tele_ensure(pr_graph *g) {
 }
 }  // namespace
 
+int set_teleport_dangling(pr_graph *g, int32_t mode) {
+  PR_TRY(tele_quiesce(g));  // the enqueued steps ran in the old mode
+  if (mode == PR_TELEPORT_DANGLING_TELEPORT) PR_TRY(prepare_tele_dangling_kernels(g));
+  g->tele_dangling = mode;
+  return PR_OK;
+}
+
 int clear_teleport(pr_graph *g) {
   PR_TRY(tele_quiesce(g));
   g->tele_on = false;  // the allocation stays (and stays counted) for the next set
+  g->tele_sum = 0.0;
   return PR_OK;
 }
 
@@ -666,6 +708,7 @@ int set_teleport_dense(pr_graph *g, const double *teleport) {
     PR_HIP(hipMemcpyAsync(g->tele.p, loc.data(), sizeof(double) * g->n_rows, hipMemcpyHostToDevice, g->stream));
     PR_HIP(hipStreamSynchronize(g->stream));
   }
+  g->tele_sum = tele_sum_dense(teleport, g->V);  // over all V IDs: the same bits on every part
   g->tele_on = true;
   return PR_OK;
 }
@@ -711,6 +754,12 @@ int set_teleport_sparse(pr_graph *g, int32_t n, const int32_t *ids, const double
     PR_HIP(hipGetLastError());
   }
   PR_HIP(hipStreamSynchronize(s));  // the staging buffers go out of scope
+  {  // ts over all V IDs from the seeds in ID order: the bits of the equal dense vector
+    std::vector<int32_t> sid((size_t)n);
+    std::vector<double> sval((size_t)n);
+    for (int32_t i = 0; i < n; ++i) sid[i] = seeds[i].first, sval[i] = values[seeds[i].second];
+    g->tele_sum = tele_sum_sparse(g->V, n, sid.data(), sval.data(), rest);
+  }
   g->tele_on = true;
   return PR_OK;
 }

@@ -27,12 +27,26 @@ __device__ __forceinline__ double dc_from_slots(const double *cin, const SlotPos
 }
 
 // r' = teleport + damping * (S + tdc), evaluated exactly as Sparky.java:233 (no contraction).
-// Personalised PageRank (pr_set_teleport): kernels instantiated with TELE = true read the row's own
-// teleport term from `tele` (row order, one double per local row, holes included) in the scalar's
-// place; the expression and its rounding are the same.  The TELE = false instantiations are the
-// kernels of a handle without a vector: they never touch `tele`.
 __device__ __forceinline__ double affine(double S, double tdc, double teleport, double damping) {
   return __dadd_rn(teleport, __dmul_rn(damping, __dadd_rn(S, tdc)));
+}
+
+// The three forms of an update site (template parameter TM of the kernels below).
+//   kTeleOff       the kernels of a handle without a vector: the scalar teleport, never touch `tele`.
+//   kTeleOn        personalised PageRank (pr_set_teleport): the row's own teleport term from `tele`
+//                  (row order, one double per local row, holes included) in the scalar's place; the
+//                  expression and its rounding are the same.  TELE in the bodies: TM != kTeleOff.
+//   kTeleDangling  the same with pr_set_teleport_dangling's mode on: the dangling mass returns along
+//                  the vector -- the row's term is q * t[row] (one rounded multiply) in the launch-wide
+//                  dc / N's place, with q = dc / ts.  These kernels receive ts = the sum of the whole
+//                  vector (pr_tele_sum.h) where the others receive n_vertices, so
+//                  `dc_from_slots(...) / n_vertices` is already q and the kernel arguments of the other
+//                  two forms stay as they are, and so does their code.
+enum : int { kTeleOff = 0, kTeleOn = 1, kTeleDangling = 2 };
+template <int TM>
+__device__ __forceinline__ double tele_dangling_term(double tdc, double tv) {
+  if constexpr (TM == kTeleDangling) return __dmul_rn(tdc, tv);
+  else return tdc;
 }
 
 typedef int pr_v4i __attribute__((ext_vector_type(4)));
@@ -73,13 +87,16 @@ __device__ __forceinline__ void load_cols(const int32_t *__restrict__ p, int32_t
 //     rows (coalesced) and fuses the in-degree-0 quirk, r' = 0.15 + 0.85 (S + dc/N) without FMA,
 //     c' = r'/d, the partial sum of r' over sink rows and the partial L1 norm.
 //   PIECE unit (PT*256 in-links of one long row): one fixed-order block sum -> piece_part.
-template <int PT, bool NT, bool TELE>
+// TM: the form of the update (kTeleOff / kTeleOn / kTeleDangling above); with kTeleDangling the
+// argument `n_vertices` carries ts, so tdc below is q = dc / ts.
+template <int PT, bool NT, int TM>
 __global__ __launch_bounds__(kThreads) void k_spmv_units(
     const Unit *__restrict__ units, const int64_t *__restrict__ rowptr,
     const int32_t *__restrict__ colp, const double *__restrict__ cin, double *__restrict__ cout,
     double *__restrict__ r, const uint32_t *__restrict__ rowinfo, double *__restrict__ piece_part,
     double2 *__restrict__ unit_part, SlotPos sp, int64_t S_pad, double n_vertices, double teleport,
     double damping, const double *__restrict__ tele) {
+  constexpr bool TELE = TM != kTeleOff;
   __shared__ double rowsum[kUnitRows];
   __shared__ int32_t lrp[kUnitRows + 1];
   __shared__ double red[kThreads / kWave];
@@ -232,7 +249,7 @@ __global__ __launch_bounds__(kThreads) void k_spmv_units(
     const double S = (lrp[k + 1] > lrp[k]) ? rowsum[k] : rold;
     double tv = teleport;
     if constexpr (TELE) tv = (k == t) ? tele0 : tele[vtx];
-    const double rn = affine(S, tdc, tv, damping);
+    const double rn = affine(S, tele_dangling_term<TM>(tdc, tv), tv, damping);
     r[vtx] = rn;
     const uint32_t d = info & kRowDegMask;
     if (d > 0) cout[vtx] = __ddiv_rn(rn, (double)d);
@@ -1008,7 +1025,7 @@ struct EpiArgs {
   const uint16_t *epos;
   const uint8_t *pmask;
   const int32_t *sbase;
-  const double *tele;  // per-row teleport terms (TELE instantiations only)
+  const double *tele;  // per-row teleport terms (kTeleOn / kTeleDangling instantiations only)
 };
 
 // Cache policy of the epilogue's LDS-DMA of the partial runs (aux bits); A/B builds only.
@@ -1032,10 +1049,11 @@ struct EpiArgs {
 // same order whichever wave, workgroup or launch ran the group: every epilogue schedule and grid
 // shape is bitwise the same (round 4's overlapped-epilogue schedules relied on it; they were
 // measured slower and removed, profiles/r04/README.md).  The body of k_epilogue_grp (below).
-template <int C, bool WALK, bool TELE>
+template <int C, bool WALK, int TM>
 __device__ __forceinline__ void epi_group(const EpiArgs &a, const PackDst &pd, int64_t gi, double tdc, double *win,
                                           double2 *__restrict__ ep_part) {
   double dcp = 0.0, l1p = 0.0;
+  constexpr bool TELE = TM != kTeleOff;
   constexpr int G = kEpiGroup, W = kEpiWin;
   constexpr int MW = mask_words<C>();  // 32-bit mask words per row
   static_assert(MW == 1 || MW == 2 || MW == 4, "mask words");
@@ -1209,7 +1227,7 @@ __device__ __forceinline__ void epi_group(const EpiArgs &a, const PackDst &pd, i
 #pragma unroll
     for (int w = 0; w < MW; ++w) any |= mw[w][g];
     if (any == 0u) Sv = rold[g];  // no in-link: subtractByKey + union keeps the old rank (Sparky.java:224-225)
-    const double rn = affine(Sv, tdc, tv[g], a.damping);
+    const double rn = affine(Sv, tele_dangling_term<TM>(tdc, tv[g]), tv[g], a.damping);
     double cn = 0.0;
     if (!(info[g] & kRowHole)) {
       a.r[L] = rn;
@@ -1267,7 +1285,9 @@ __device__ __forceinline__ void epi_group(const EpiArgs &a, const PackDst &pd, i
 #else
 #define PR_EPI_BOUNDS(NT) __launch_bounds__(NT, 4)
 #endif
-template <int C, bool WALK, int NT, bool TELE>
+// TM: the form of the update (kTeleOff / kTeleOn / kTeleDangling); with kTeleDangling the argument
+// `n_vertices` carries ts, so tdc below is q = dc / ts.
+template <int C, bool WALK, int NT, int TM>
 __global__ PR_EPI_BOUNDS(NT) void k_epilogue_grp(
     int64_t nblk, int64_t g_lo, int64_t g_hi, const double *__restrict__ partial, const void *__restrict__ rmask_v,
     const int32_t *__restrict__ cbase, const uint32_t *__restrict__ rowinfo, double *__restrict__ r,
@@ -1288,7 +1308,7 @@ __global__ PR_EPI_BOUNDS(NT) void k_epilogue_grp(
   // order: the group of each dispatch position (heaviest first, plan_epi_order); the group's
   // partials go to its own ep_part slot, so the order changes no sum
   for (int64_t k = g_lo + (int64_t)blockIdx.x * NW + wv; k < g_hi; k += nw)
-    epi_group<C, WALK, TELE>(a, pd, order ? (int64_t)order[k] : k, tdc, win, ep_part);
+    epi_group<C, WALK, TM>(a, pd, order ? (int64_t)order[k] : k, tdc, win, ep_part);
 }
 
 // Build-time plan of the per-row walk (WALK above), one wave per group of G 64-row blocks.
@@ -1369,28 +1389,31 @@ __global__ __launch_bounds__(kEpiThreads) void k_epi_walk_plan(int64_t nblk, con
 using EpiGrpFn = void (*)(int64_t, int64_t, int64_t, const double *, const void *, const int32_t *, const uint32_t *, double *,
                           double *, const double *, SlotPos, double, double, double, double2 *, const int64_t *,
                           const uint16_t *, const uint8_t *, const int32_t *, const int32_t *, PackDst, const double *);
-template <int C, bool TELE>
+template <int C, int TM>
 inline EpiGrpFn epi_grp_kernel_c(bool walk, bool narrow) {
   if constexpr (C <= kWave) {
     if (narrow)
-      return walk ? k_epilogue_grp<C, true, kEpiThreadsNarrow, TELE> : k_epilogue_grp<C, false, kEpiThreadsNarrow, TELE>;
-    if (walk) return k_epilogue_grp<C, true, kEpiThreads, TELE>;
+      return walk ? k_epilogue_grp<C, true, kEpiThreadsNarrow, TM> : k_epilogue_grp<C, false, kEpiThreadsNarrow, TM>;
+    if (walk) return k_epilogue_grp<C, true, kEpiThreads, TM>;
   }
-  return k_epilogue_grp<C, false, kEpiThreads, TELE>;
+  return k_epilogue_grp<C, false, kEpiThreads, TM>;
 }
-template <bool TELE>
+template <int TM>
 inline EpiGrpFn epi_grp_kernel_t(int C, bool walk, bool narrow) {
   switch (C) {
-    case 8: return epi_grp_kernel_c<8, TELE>(walk, narrow);
-    case 16: return epi_grp_kernel_c<16, TELE>(walk, narrow);
-    case 32: return epi_grp_kernel_c<32, TELE>(walk, narrow);
-    case 64: return epi_grp_kernel_c<64, TELE>(walk, narrow);
-    default: return epi_grp_kernel_c<128, TELE>(false, false);
+    case 8: return epi_grp_kernel_c<8, TM>(walk, narrow);
+    case 16: return epi_grp_kernel_c<16, TM>(walk, narrow);
+    case 32: return epi_grp_kernel_c<32, TM>(walk, narrow);
+    case 64: return epi_grp_kernel_c<64, TM>(walk, narrow);
+    default: return epi_grp_kernel_c<128, TM>(false, false);
   }
 }
-// tele: the instantiations that read per-row teleport terms (a handle with pr_set_teleport in force)
-inline EpiGrpFn epi_grp_kernel(int C, bool walk, bool narrow, bool tele = false) {
-  return tele ? epi_grp_kernel_t<true>(C, walk, narrow) : epi_grp_kernel_t<false>(C, walk, narrow);
+// tele: the form of the update (kTeleOff; kTeleOn: a handle with pr_set_teleport in force;
+// kTeleDangling: the same with pr_set_teleport_dangling's mode on, which takes ts for n_vertices)
+inline EpiGrpFn epi_grp_kernel(int C, bool walk, bool narrow, int tele = kTeleOff) {
+  return tele == kTeleDangling ? epi_grp_kernel_t<kTeleDangling>(C, walk, narrow)
+         : tele == kTeleOn     ? epi_grp_kernel_t<kTeleOn>(C, walk, narrow)
+                               : epi_grp_kernel_t<kTeleOff>(C, walk, narrow);
 }
 
 }  // namespace pr

@@ -1,7 +1,7 @@
 // pagerank -- process-level drop-in for the Sparky.java Spark job (C++ host).
 //
 //   pagerank <input-path> [iterations=10] [--format=edges|ccjson] [--out DIR]
-//            [--save-every-iter] [--dangling=local|none] [--device N] [--quiet] [--stats]
+//            [--save-every-iter] [--dangling=local|none|seeds] [--device N] [--quiet] [--stats]
 //            [--resume DIR/PageRank<i>] [--devices D0,D1,...] [--top K] [--seeds FILE]
 //            [--seed-set FILE]... [--exclude-seeds] [--tol X] [--seed-queue LISTFILE [--slots W]]
 //            [--dangling-to-seeds] [--mix W0,W1,...]...
@@ -26,10 +26,17 @@
 // --seeds FILE: personalised PageRank.  FILE lists the seed URLs, one "url" or "url weight" per line
 // (weight > 0, default 1; blank lines and '#' lines skipped): the teleport mass 0.15 N goes to the
 // seeds in proportion to their weights and every other URL's teleport term is 0
-// (prh_seed_teleport, pr_set_teleport_sparse); the dangling term stays uniform.  The file is read
-// and checked before the graph is created: a bad one exits with status 2 without touching a GPU.
-// Combines with every other option; outputs have the same form as without it.
+// (prh_seed_teleport, pr_set_teleport_sparse); the dangling term stays uniform unless --dangling=seeds
+// is given.  The file is read and checked before the graph is created: a bad one exits with status 2
+// without touching a GPU.  Combines with every other option; outputs have the same form as without it.
 //   pagerank edges.txt 20 --seeds seeds.txt --top 100
+// --dangling=seeds (needs --seeds, else a usage error before any GPU work): the run's dangling mass
+// returns to the --seeds set in proportion to the weights, instead of being spread over all URLs
+// (pr_set_teleport_dangling, PR_TELEPORT_DANGLING_TELEPORT): textbook personalised PageRank, in which
+// a URL the seeds cannot reach drains to 0.  The graph counts its dangling mass as with
+// --dangling=local.  Works with --devices, --top, --out and --resume; output format unchanged.  For
+// --seed-set and --seed-queue the same choice is --dangling-to-seeds.
+//   pagerank edges.txt 20 --seeds seeds.txt --dangling=seeds --top 100
 // --seed-set FILE (1 to 16 times): batched personalised PageRank.  Every FILE is a seed file as for
 // --seeds and gives one personalised ranking; all of them run as one batch (pr_batch_*), one pass
 // over the graph per iteration for all sets.  Per set, in command-line order, the listing is a line
@@ -65,8 +72,8 @@
 // (pr_batch_set_dangling, PR_BATCH_DANGLING_TELEPORT), instead of being spread over all URLs: a URL the
 // seeds cannot reach keeps rank 0.  A set whose teleport terms sum to 0 or overflow keeps the uniform term; with
 // --dangling=none there is no dangling mass and the option changes nothing.  The mode is the whole
-// run's, not a set's; --seeds (the engine's own iteration) keeps the uniform term.  Output format
-// unchanged.
+// run's, not a set's; for --seeds (the engine's own iteration) the same choice is --dangling=seeds.
+// Output format unchanged.
 //   pagerank edges.txt 20 --seed-set alice.txt --seed-set bob.txt --top 100 --dangling-to-seeds
 // --mix W0,W1,... (1 to 16 times; needs --seed-set and --top, not with --seed-queue; exactly one finite
 // number per --seed-set file; anything else is a usage error before any GPU work): after the per-set
@@ -96,6 +103,7 @@ struct Options {
   bool save_every = false, quiet = false, stats = false;
   bool exclude_seeds = false;  // --exclude-seeds
   bool dangling_to_seeds = false;  // --dangling-to-seeds
+  bool dangling_seeds = false;     // --dangling=seeds (flags stay PR_DANGLING_LOCAL)
   bool has_tol = false;        // --tol X: `iterations` is the cap
   double tol = 0.0;
   uint32_t flags = PR_DANGLING_LOCAL;
@@ -127,8 +135,10 @@ std::vector<int> parse_devices(const std::string &s) {
   if (msg) std::fprintf(stderr, "pagerank: %s\n", msg);
   std::fprintf(stderr,
                "usage: pagerank <input-path> [iterations=10] [--format=edges|ccjson] [--out DIR]\n"
-               "                [--save-every-iter] [--dangling=local|none] [--device N] [--quiet] [--stats]\n"
+               "                [--save-every-iter] [--dangling=local|none|seeds] [--device N] [--quiet] [--stats]\n"
                "                [--resume DIR/PageRank<i>] [--devices D0,D1,...] [--top K] [--seeds FILE]\n"
+               "                (--dangling=seeds, with --seeds: the dangling mass returns to the seeds instead of all\n"
+               "                URLs)\n"
                "                [--seed-set FILE]...  (1 to 16 seed files, run as one batch; not with --seeds,\n"
                "                --devices, --resume or --save-every-iter)\n"
                "                [--exclude-seeds]  (with --seed-set and --top: a set's own seeds are left out of\n"
@@ -140,7 +150,7 @@ std::vector<int> parse_devices(const std::string &s) {
                "                not with --seeds, --seed-set, --devices, --resume or --save-every-iter)\n"
                "                [--dangling-to-seeds]  (with --seed-set or --seed-queue: a set's dangling mass returns to\n"
                "                its own seeds instead of all URLs; a set whose teleport terms sum to 0 or overflow keeps the\n"
-               "                uniform term; the whole run's mode, not a set's; --seeds keeps the uniform term)\n"
+               "                uniform term; the whole run's mode, not a set's; for --seeds: --dangling=seeds)\n"
                "                [--mix W0,W1,...]...  (with --seed-set and --top, 1 to 16 times: also list the K best\n"
                "                URLs of the weighted blend of the sets' rankings, one finite weight per --seed-set;\n"
                "                not with --seed-queue)\n");
@@ -179,8 +189,9 @@ Options parse(int argc, char **argv) {
     else if (a == "--stats") o.stats = true;
     else if (a == "--exclude-seeds") o.exclude_seeds = true;
     else if (a == "--dangling-to-seeds") o.dangling_to_seeds = true;
-    else if (a == "--dangling=local") o.flags = PR_DANGLING_LOCAL;
-    else if (a == "--dangling=none") o.flags = PR_DANGLING_NONE;
+    else if (a == "--dangling=local") o.flags = PR_DANGLING_LOCAL, o.dangling_seeds = false;
+    else if (a == "--dangling=none") o.flags = PR_DANGLING_NONE, o.dangling_seeds = false;
+    else if (a == "--dangling=seeds") o.flags = PR_DANGLING_LOCAL, o.dangling_seeds = true;
     else if (a == "--device" && i + 1 < argc) o.device = std::atoi(argv[++i]);
     else if (a == "--resume" && i + 1 < argc) o.resume = argv[++i];
     else if (a.rfind("--resume=", 0) == 0) o.resume = a.substr(9);
@@ -227,6 +238,10 @@ Options parse(int argc, char **argv) {
   if (o.iterations < 0) usage("iterations must be >= 0");
   if (o.dangling_to_seeds && o.seed_sets.empty() && o.seed_queue.empty())
     usage("--dangling-to-seeds needs --seed-set or --seed-queue");
+  if (o.dangling_seeds && o.seeds.empty())
+    usage(o.seed_sets.empty() && o.seed_queue.empty()
+              ? "--dangling=seeds needs --seeds"
+              : "--dangling=seeds needs --seeds; with --seed-set or --seed-queue use --dangling-to-seeds");
   if (!o.mixes.empty()) {
     if (!o.seed_queue.empty()) usage("--mix does not combine with --seed-queue");
     if (o.seed_sets.empty() || o.top == 0) usage("--mix needs --seed-set and --top");
@@ -309,6 +324,8 @@ int run_group(const Options &o, const prh_edges *edges, const Seeds &seeds, cons
   const bool want = !o.out.empty();
   for (int p = 0; p < P && rc == PR_OK && seeds.n > 0; ++p)  // every part, the same arguments
     rc = pr_set_teleport_sparse(parts[p], seeds.n, seeds.ids, seeds.values.data(), 0.0);
+  for (int p = 0; p < P && rc == PR_OK && o.dangling_seeds; ++p)  // --dangling=seeds: every part alike
+    rc = pr_set_teleport_dangling(parts[p], PR_TELEPORT_DANGLING_TELEPORT);
   if (rc == PR_OK) rc = pr_group_reset(parts.data(), P, 0.15, 0.85, init);
   for (int it = 0; it < n_run && rc == PR_OK; ++it) {
     const auto t0 = std::chrono::steady_clock::now();
@@ -654,7 +671,9 @@ int main(int argc, char **argv) {
       prh_free(edges);
       return 1;
     }
-    if (seeds.n > 0 && (rc = pr_set_teleport_sparse(g, seeds.n, seeds.ids, seeds.values.data(), 0.0)) != PR_OK) {
+    if (seeds.n > 0) rc = pr_set_teleport_sparse(g, seeds.n, seeds.ids, seeds.values.data(), 0.0);
+    if (rc == PR_OK && o.dangling_seeds) rc = pr_set_teleport_dangling(g, PR_TELEPORT_DANGLING_TELEPORT);
+    if (rc != PR_OK) {
       std::fprintf(stderr, "pagerank: --seeds: (%d) %s\n", rc, pr_last_error());
       pr_graph_destroy(g);
       prh_free_seeds(seeds.ids, nullptr);

@@ -61,6 +61,7 @@ EXPORTED = [
     "pr_graph_destroy", "pr_gen_rmat", "pr_gen_er", "pr_gen_chunglu", "pr_intern_device", "pr_group_reset",
     "pr_group_step", "pr_group_sync", "pr_get_topk", "pr_group_topk", "pr_topk_merge",
     "pr_set_teleport", "pr_set_teleport_sparse",
+    "pr_set_teleport_dangling", "pr_get_teleport_dangling", "pr_get_teleport_sum",
     "pr_batch_create", "pr_batch_set_teleport", "pr_batch_set_teleport_sparse", "pr_batch_reset", "pr_batch_step",
     "pr_batch_sync", "pr_batch_get_ranks", "pr_batch_get_norms", "pr_batch_get_topk", "pr_batch_info",
     "pr_batch_destroy", "pr_batch_set_exclude", "pr_batch_get_topk_all", "pr_batch_step_until",
@@ -76,6 +77,10 @@ BATCH_MAX_MIXES = 16  # PR_BATCH_MAX_MIXES
 PR_BATCH_DANGLING_UNIFORM = 0
 PR_BATCH_DANGLING_TELEPORT = 1
 BATCH_DANGLING_MODES = {"uniform": PR_BATCH_DANGLING_UNIFORM, "teleport": PR_BATCH_DANGLING_TELEPORT}
+# pr_set_teleport_dangling's modes (PR_TELEPORT_DANGLING_*), by the name PageRankGraph.set_teleport_dangling takes
+PR_TELEPORT_DANGLING_UNIFORM = 0
+PR_TELEPORT_DANGLING_TELEPORT = 1
+TELEPORT_DANGLING_MODES = {"uniform": PR_TELEPORT_DANGLING_UNIFORM, "teleport": PR_TELEPORT_DANGLING_TELEPORT}
 
 ITER_CB = ctypes.CFUNCTYPE(None, ctypes.c_int32, ctypes.POINTER(ctypes.c_double), ctypes.c_double,
                            ctypes.c_double, ctypes.c_double, ctypes.c_void_p)
@@ -160,6 +165,9 @@ def load() -> ctypes.CDLL:
         "pr_topk_merge": ([i32, P, P, P, i32, P, P, P], ctypes.c_int),
         "pr_set_teleport": ([P, P], ctypes.c_int),
         "pr_set_teleport_sparse": ([P, i32, P, P, dbl], ctypes.c_int),
+        "pr_set_teleport_dangling": ([P, i32], ctypes.c_int),
+        "pr_get_teleport_dangling": ([P, P], ctypes.c_int),
+        "pr_get_teleport_sum": ([P, P], ctypes.c_int),
         "pr_batch_create": ([P, i32, P], ctypes.c_int),
         "pr_batch_set_teleport": ([P, i32, P], ctypes.c_int),
         "pr_batch_set_teleport_sparse": ([P, i32, i32, P, P, dbl], ctypes.c_int),

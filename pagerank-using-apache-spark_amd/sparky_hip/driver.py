@@ -1,7 +1,7 @@
 """Process-level drop-in for the Spark job (Python host; the C++ CLI ``pagerank`` is the same).
 
 CLI: ``python -m sparky_hip <input-path> [iterations=10] [--format edges|ccjson]
-[--out DIR] [--save-every-iter] [--dangling=local|none] [--device N] [--quiet]
+[--out DIR] [--save-every-iter] [--dangling=local|none|seeds] [--device N] [--quiet]
 [--resume DIR/PageRank<i>] [--devices D0,D1,...] [--top K] [--seeds FILE] [--seed-set FILE]...
 [--exclude-seeds] [--tol X] [--seed-queue LISTFILE [--slots W]] [--dangling-to-seeds]
 [--mix W0,W1,...]...``
@@ -24,9 +24,15 @@ CLI: ``python -m sparky_hip <input-path> [iterations=10] [--form
 * ``--seeds FILE``: personalised PageRank.  One ``url`` or ``url weight`` per line (weight > 0,
   default 1; blank and ``#`` lines skipped): the teleport mass 0.15 N goes to the seeds in
   proportion to their weights, every other URL's teleport term is 0 (``prh_seed_teleport``, then
-  ``set_teleport_sparse``); the dangling term stays uniform.  The file is read and checked before
-  the graph is created: a bad one exits with status 2 without touching a GPU.  Same outputs as the
-  C++ CLI: ``pagerank edges.txt 20 --seeds seeds.txt --top 100``.
+  ``set_teleport_sparse``); the dangling term stays uniform unless ``--dangling=seeds`` is given.
+  The file is read and checked before the graph is created: a bad one exits with status 2 without
+  touching a GPU.  Same outputs as the C++ CLI: ``pagerank edges.txt 20 --seeds seeds.txt --top 100``.
+* ``--dangling=seeds`` (needs ``--seeds``, else a usage error before any GPU work): the run's dangling
+  mass returns to the ``--seeds`` set in proportion to the weights instead of being spread over all
+  URLs (``PageRankGraph.set_teleport_dangling("teleport")``): textbook personalised PageRank, in
+  which a URL the seeds cannot reach drains to 0.  The graph counts its dangling mass as with
+  ``--dangling=local``.  Works with ``--devices``, ``--top``, ``--out`` and ``--resume``; same bytes as
+  the C++ CLI.  For ``--seed-set`` and ``--seed-queue`` the same choice is ``--dangling-to-seeds``.
 * ``--seed-set FILE`` (1 to 16 times): batched personalised PageRank.  Every FILE is a seed file as
   for ``--seeds`` and gives one personalised ranking; all of them run as one batch
   (``PageRankBatch``), one pass over the graph per iteration for all sets.  Per set, in
@@ -61,8 +67,8 @@ CLI: ``python -m sparky_hip <input-path> [iterations=10] [--form
   (``PageRankBatch.set_dangling("teleport")``), instead of being spread over all URLs: a URL the
   seeds cannot reach keeps rank 0.  A set whose teleport terms sum to 0 or overflow keeps the uniform term; with
   ``--dangling=none`` there is no dangling mass and the option changes nothing.  The mode is the
-  whole run's, not a set's; ``--seeds`` (the engine's own iteration) keeps the uniform term.  Output
-  format unchanged, same bytes as the C++ CLI.
+  whole run's, not a set's; for ``--seeds`` (the engine's own iteration) the same choice is
+  ``--dangling=seeds``.  Output format unchanged, same bytes as the C++ CLI.
 * ``--mix W0,W1,...`` (1 to 16 times; needs ``--seed-set`` and ``--top``, not with ``--seed-queue``; exactly
   one finite number per ``--seed-set`` file; anything else is a usage error before any GPU work): after
   the per-set listings, mix i prints ``# mix <i>: <the weights as given>`` and the ``--top`` listing of
@@ -188,7 +194,7 @@ def saved_iteration(path: str) -> int:
     return -1
 
 
-def _run_group(edges, devices, dangling, n_run, init, cb, want_ranks, top=0, seeds=None):
+def _run_group(edges, devices, dangling, n_run, init, cb, want_ranks, top=0, seeds=None, dangling_seeds=False):
     """--devices: one part per listed device, one process (pr_group_*); the callback gets the
     merged ranks of every part after each iteration, as with PageRankGraph.run.  Returns the
     final ranks, or with top > 0 the (ids, ranks) of PartGroup.topk(top)."""
@@ -201,6 +207,8 @@ def _run_group(edges, devices, dangling, n_run, init, cb, want_ranks, top=0, see
         grp = PartGroup(parts)
         if seeds is not None:
             grp.set_teleport_sparse(*seeds)
+        if dangling_seeds:  # --dangling=seeds: every part alike
+            grp.set_teleport_dangling("teleport")
         grp.reset(init_ranks=init)
         for it in range(n_run):
             grp.step(1)
@@ -333,7 +341,8 @@ def main(argv=None) -> int:
     ap.add_argument("--format", choices=["edges", "ccjson"], default="edges")
     ap.add_argument("--out", default=None)
     ap.add_argument("--save-every-iter", action="store_true")
-    ap.add_argument("--dangling", choices=["local", "none"], default="local")
+    ap.add_argument("--dangling", choices=["local", "none", "seeds"], default="local",
+                    help="seeds (with --seeds): the run's dangling mass returns to the seeds instead of all URLs")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--quiet", action="store_true", help="omit the '<url> has rank' lines")
     ap.add_argument("--resume", default=None, metavar="DIR", help="start from saved (url,rank) part files")
@@ -357,7 +366,7 @@ def main(argv=None) -> int:
     ap.add_argument("--dangling-to-seeds", action="store_true",
                     help="with --seed-set or --seed-queue: a set's dangling mass returns to its own seeds instead of "
                          "all URLs; a set whose teleport terms sum to 0 or overflow keeps the uniform term; the whole run's "
-                         "mode, not a set's; --seeds keeps the uniform term")
+                         "mode, not a set's; for --seeds: --dangling=seeds")
     ap.add_argument("--mix", action="append", default=None, metavar="W0,W1,...",
                     help="with --seed-set and --top, 1 to 16 times: also list the K best URLs of the weighted blend of "
                          "the sets' rankings, one finite weight per --seed-set; not with --seed-queue")
@@ -387,6 +396,12 @@ def main(argv=None) -> int:
             ap.error("--tol needs --seed-set")
     if a.dangling_to_seeds and not (a.seed_set or a.seed_queue is not None):
         ap.error("--dangling-to-seeds needs --seed-set or --seed-queue")
+    dangling_seeds = a.dangling == "seeds"
+    if dangling_seeds:
+        if a.seeds is None:
+            ap.error("--dangling=seeds needs --seeds" if not (a.seed_set or a.seed_queue is not None) else
+                     "--dangling=seeds needs --seeds; with --seed-set or --seed-queue use --dangling-to-seeds")
+        a.dangling = "local"  # the graph counts its dangling mass; the handle's mode returns it to the seeds
     if a.seed_queue is not None:
         if a.seeds is not None or a.seed_set or a.devices is not None or a.resume or a.save_every_iter:
             ap.error("--seed-queue does not combine with --seeds, --seed-set, --devices, --resume or --save-every-iter")
@@ -480,6 +495,8 @@ def main(argv=None) -> int:
                            keep_canonical=False) as g:
             if seeds is not None:
                 g.set_teleport_sparse(*seeds)
+            if dangling_seeds:
+                g.set_teleport_dangling("teleport")
             if top and not a.out:  # no part file: the ranks stay on the device
                 g.reset(init_ranks=init)
                 for it in range(n_run):
@@ -490,7 +507,7 @@ def main(argv=None) -> int:
             if top:
                 ranks = g.topk(top)
     else:
-        ranks = _run_group(edges, devices, a.dangling, n_run, init, cb, bool(a.out), top, seeds)
+        ranks = _run_group(edges, devices, a.dangling, n_run, init, cb, bool(a.out), top, seeds, dangling_seeds)
     out.flush()
     if not a.quiet and top:
         edges.write_has_rank_ids(None, *ranks)

@@ -235,6 +235,31 @@ class PageRankGraph:
         i, v = _sparse_arrays(ids, values)
         check(_lib.load().pr_set_teleport_sparse(self._h, int(i.shape[0]), _ptr(i), _ptr(v), float(rest)))
 
+    def set_teleport_dangling(self, mode: str) -> None:
+        """pr_set_teleport_dangling: where the dangling mass goes while a teleport vector is set.
+        "uniform" (the default): dc / N to every vertex.  "teleport": along the vector,
+        r' = t + damping * (S + (dc / ts) * t) with ts = teleport_sum() -- textbook personalised
+        PageRank.  Without a vector, on a dangling="none" graph, or with a ts that is 0 or not finite
+        the uniform kernels run.  The mode belongs to the handle: it survives reset(), run() and
+        set_teleport(None), and holds from the next step on."""
+        if mode not in _lib.TELEPORT_DANGLING_MODES:
+            raise ValueError("mode must be 'uniform' or 'teleport'")
+        check(_lib.load().pr_set_teleport_dangling(self._h, _lib.TELEPORT_DANGLING_MODES[mode]))
+
+    @property
+    def teleport_dangling(self) -> str:
+        """The mode set_teleport_dangling set: "uniform" or "teleport"."""
+        m = ctypes.c_int32(0)
+        check(_lib.load().pr_get_teleport_dangling(self._h, ctypes.byref(m)))
+        return next(k for k, v in _lib.TELEPORT_DANGLING_MODES.items() if v == m.value)
+
+    def teleport_sum(self) -> float:
+        """pr_get_teleport_sum: ts, the sum of the teleport vector in force over all V vertices in
+        the library's fixed order (the same bits on every part); 0.0 without a vector."""
+        x = ctypes.c_double(0.0)
+        check(_lib.load().pr_get_teleport_sum(self._h, ctypes.byref(x)))
+        return x.value
+
     def topk(self, k: int):
         """pr_get_topk: the k highest-ranked vertices of this part, selected on the device -- rank
         descending, ties by original ID ascending.  Returns (ids int32[n], ranks float64[n]) with
@@ -397,6 +422,11 @@ class PartGroup:
         i, v = _sparse_arrays(ids, values)
         for p in self.parts:
             p.set_teleport_sparse(i, v, rest)
+
+    def set_teleport_dangling(self, mode: str) -> None:
+        """PageRankGraph.set_teleport_dangling on every part (local to a part, like the vector)."""
+        for p in self.parts:
+            p.set_teleport_dangling(mode)
 
     def topk(self, k: int):
         """pr_group_topk: every part's top-K list, merged; (ids int32[n], ranks float64[n])."""
